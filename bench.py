@@ -252,6 +252,45 @@ def extra_configs(torch, pa, ctx, device, steps=5):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs stays well under 64 MB in all (the .npy headers included)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, key_cells, key_null, aggs):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step (Context.groupby_fetch:
+    key cells [n_keys, G] u64, key null flags [n_keys, G] u8, aggregates [n_aggs, G] f64), as .npy files that two
+    builds can be compared with.  The groups come in the engine's order, so they are sorted by key first; if they
+    do not fit the budget, a fixed seeded sample of the sorted groups is written.  64-bit key cells do not fit a
+    float64, so each is written as two exact halves (group_key_hi32, group_key_lo32)."""
+    import numpy as np
+
+    def host(a, dtype):
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        return a.view(dtype) if a.dtype.itemsize == np.dtype(dtype).itemsize else a.astype(dtype)
+
+    kc, kn, oa = host(key_cells, np.uint64), host(key_null, np.uint8), host(aggs, np.float64)
+    n_keys, n_aggs, g = kc.shape[0], oa.shape[0], kc.shape[1]
+    order = np.lexsort(np.vstack([kc, kn.astype(np.uint64)])[::-1]) if g else np.zeros(0, np.int64)   # primary: key cell 0
+    per_group = n_keys * (8 + 8 + 4) + n_aggs * 8
+    n_out = min(g, DUMP_BUDGET_BYTES // per_group)
+    if n_out < g:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(g, n_out, replace=False))
+    else:
+        pick = np.arange(g)
+    sel = order[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "n_groups": np.array([g], np.float64),
+        "group_rank": pick.astype(np.float64),                     # position of each written group in key order
+        "group_key_hi32": (kc[:, sel] >> np.uint64(32)).astype(np.float64),
+        "group_key_lo32": (kc[:, sel] & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "group_key_null": kn[:, sel].astype(np.float32),
+        "aggregates": oa[:, sel],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 _REAL_STDOUT = None
 
 
@@ -293,6 +332,8 @@ def dry_run(args):
     tmax = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *dgb.engine.groupby_fetch())
     if rank == 0:
         print(json.dumps({"metric": "Mrows/sec groupby-agg", "value": n * world / (dt / args.steps) / 1e6, "unit": "Mrows/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -347,7 +388,16 @@ def main():
                          "the configuration north_star names for the 8-GPU radix all-to-all")
     ap.add_argument("--join-strategy", choices=["auto", "allgather", "shuffle"], default="auto",
                     help="N > 1, --workload join: replicate the build side, or shuffle both sides to the owner of their key")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: groups sorted by key, a fixed seeded sample when they do not fit); needs --gpus 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (with more ranks each one holds only its share of the groups)")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -431,6 +481,8 @@ def main():
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *ctx.groupby_fetch(to_device=False))
 
     if rank == 0:
         k = args.steps
@@ -534,6 +586,8 @@ def bench_join(args, torch, pa, dist, rank, local_rank, world, device):
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *out)
     if rank == 0:
         k = args.steps
         n_groups = int(out[0].shape[1])

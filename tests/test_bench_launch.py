@@ -33,3 +33,66 @@ def test_world_size_mismatch_is_an_error():
     p = _run(["--gpus", "2"], {"PANDRS_BENCH_BACKEND": "gloo", "RANK": "0", "WORLD_SIZE": "3"})
     assert p.returncode != 0
     assert b"WORLD_SIZE" in p.stderr
+
+
+def _free_port():
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def test_dump_outputs_writes_the_last_step_deterministically(tmp_path):
+    """--dump-outputs DIR (rehearsed with the numpy stand-in engine at world 1): float .npy files of what the last timed
+    step returned, groups in key order, the same arrays from two runs with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "20000", "--groups", "500", "--cols", "2",
+                  "--dump-outputs", str(d)],
+                 {"PANDRS_BENCH_BACKEND": "gloo", "RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1",
+                  "MASTER_PORT": str(_free_port())})
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        rec = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.strip()][-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"n_groups.npy", "group_rank.npy", "group_key_hi32.npy", "group_key_lo32.npy", "group_key_null.npy", "aggregates.npy"}
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    g = int(a["n_groups.npy"][0])
+    assert 0 < g <= 500 and a["aggregates.npy"].shape == (8, g)        # 2 cols x sum/mean/min/max, every group fits
+    key = a["group_key_hi32.npy"][0].astype(np.uint64) << np.uint64(32) | a["group_key_lo32.npy"][0].astype(np.uint64)
+    assert np.all(np.diff(key) > 0)
+    s, m, lo, hi = a["aggregates.npy"][:4]
+    assert np.all(lo <= m) and np.all(m <= hi) and np.all(s >= lo - 1e-9)
+
+
+def test_dump_outputs_samples_large_results_under_64_mb(tmp_path):
+    """A result larger than the budget is written as a fixed seeded sample of the key-ordered groups."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(7)
+    g = 600_000
+    keys = rng.permutation(np.arange(g, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15))[None, :]
+    aggs = np.vstack([keys[0].astype(np.float64) + i for i in range(16)])
+    outs = []
+    for run, perm in (("a", np.arange(g)), ("b", rng.permutation(g))):          # the engine's group order must not matter
+        d = tmp_path / run
+        bench.dump_outputs(str(d), keys[:, perm], np.zeros((1, g), np.uint8), aggs[:, perm])
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64_000_000
+        outs.append({f.name: np.load(f) for f in d.glob("*.npy")})
+    a, b = outs
+    assert 0 < a["group_rank.npy"].size < g and int(a["n_groups.npy"][0]) == g
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    key = a["group_key_hi32.npy"][0].astype(np.uint64) << np.uint64(32) | a["group_key_lo32.npy"][0].astype(np.uint64)
+    assert np.array_equal(key, np.sort(keys[0])[a["group_rank.npy"].astype(np.int64)])
+    assert np.array_equal(a["aggregates.npy"][3], key.astype(np.float64) + 3)

@@ -1,18 +1,99 @@
 """The Rust shim shipped as files (integration/rust/): hip_ffi.rs must declare EXACTLY what include/pandrs_hip.h
 declares — every function (name, arity, parameter names and types, return type), every struct (field names, types,
 order) and every constant — checked mechanically, because this image has no Rust toolchain to compile it (so Rust
-SYNTAX beyond the generated declarations is not verified here).  The three seam patches must still apply to the
-reference tree when it is present (it is not on the GPU box)."""
+SYNTAX beyond the generated declarations is not verified here).  The seam patches must still apply to the
+reference tree, and what the shim touches must exist there: both are checked against facts about the reference
+stored in tests/golden/reference_shim_facts.json (names and SHA-256 digests, no source text; written by
+tests/golden/make_reference_facts.py, which also proves that these checks give what they give on the patched
+reference files themselves)."""
+import hashlib
 import importlib.util
+import json
 import os
-import shutil
-import subprocess
-import tempfile
-
-import pytest
+import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUST = os.path.join(ROOT, "integration", "rust")
+FACTS = os.path.join(ROOT, "tests", "golden", "reference_shim_facts.json")
+PATCHED = ("src/optimized/split_dataframe/group/aggregation.rs", "src/optimized/split_dataframe/join.rs", "src/optimized/lazy.rs",
+           "src/optimized/split_dataframe/group/types.rs", "src/optimized/split_dataframe/group/grouping.rs")
+
+
+def _facts():
+    with open(FACTS) as f:
+        return json.load(f)
+
+
+def _parse_patch(path):
+    """A unified diff of ONE file -> (path in the tree, [hunk]); hunk = {old_start, old_len, old, new, removed, added}."""
+    rel, hunks, h = None, [], None
+    for line in open(path).read().split("\n"):
+        if line.startswith("--- "):
+            continue
+        if line.startswith("+++ "):
+            rel = line[4:].split("\t")[0][2:]          # b/<path>
+        elif line.startswith("@@"):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            h = {"old_start": int(m.group(1)), "old_len": int(m.group(2) or 1), "old": [], "new": [], "removed": [], "added": []}
+            hunks.append(h)
+        elif h is not None and line.startswith("\\"):
+            continue                                    # "\ No newline at end of file"
+        elif h is not None and (line[:1] in (" ", "-", "+") or line == ""):
+            tag, text = (line[:1] or " "), line[1:]
+            if tag in " -":
+                h["old"].append(text)
+            if tag in " +":
+                h["new"].append(text)
+            if tag == "-":
+                h["removed"].append(text)
+            if tag == "+":
+                h["added"].append(text)
+    for h in hunks:      # a trailing empty string is the file's final newline, not a context line
+        while len(h["old"]) > h["old_len"] and h["old"][-1] == "" and h["new"] and h["new"][-1] == "":
+            h["old"].pop()
+            h["new"].pop()
+    return rel, hunks
+
+
+def _lines_digest(lines):
+    return hashlib.sha256(("\n".join(lines) + "\n").encode()).hexdigest()
+
+
+def _bracket_counts(text):
+    """{}, (), [] outside comments, string and char literals."""
+    text = re.sub(r'"(?:[^"\\]|\\.)*"', '""', re.sub(r"//[^\n]*", "", text))
+    text = re.sub(r"'(?:[^'\\]|\\.)'", "' '", text)
+    return {c: text.count(c) for c in "{}()[]"}
+
+
+def _patched(facts):
+    """Applies every seam patch to the stored facts about its reference file.  Each hunk's old side must be, digest for
+    digest, the reference lines at its position (no offset, no fuzz).  -> {path: (text of the hunks' new sides, bracket
+    counts of the whole patched file, the crate types its names resolve to)}"""
+    out = {}
+    for p in sorted(f for f in os.listdir(os.path.join(RUST, "patches")) if f.endswith(".patch")):
+        rel, hunks = _parse_patch(os.path.join(RUST, "patches", p))
+        target = facts["patch_targets"][rel]
+        assert rel not in out, "%s: two patches touch %s" % (p, rel)
+        assert [(h["old_start"], h["old_len"]) for h in hunks] == [(t["old_start"], t["old_len"]) for t in target["hunks"]], \
+            "%s: its hunks no longer sit where they were taken against the reference" % p
+        for i, (h, t) in enumerate(zip(hunks, target["hunks"])):
+            assert len(h["old"]) == h["old_len"] and h["old_start"] + h["old_len"] - 1 <= target["lines"], (p, i)
+            assert _lines_digest(h["old"]) == t["sha256"], "%s hunk %d does not apply: its old side differs from the reference" % (p, i)
+        brackets = dict(target["brackets"])
+        removed = _bracket_counts("\n".join(x for h in hunks for x in h["removed"]))
+        added = _bracket_counts("\n".join(x for h in hunks for x in h["added"]))
+        for c in brackets:
+            brackets[c] += added[c] - removed[c]
+        scope = dict(target["scope"])
+        module = _module_of(rel)
+        for name in _names_in_scope("\n".join(x for h in hunks for x in h["removed"]), module):
+            scope.pop(name, None)
+        scope.update({k: v for k, v in _names_in_scope("\n".join(x for h in hunks for x in h["added"]), module).items()
+                      if k in _CRATE_TYPES})
+        out[rel] = ("\n\x00\n".join("\n".join(h["new"]) for h in hunks), brackets, scope)
+    assert sorted(out) == sorted(PATCHED), sorted(out)
+    return out
 
 
 def _gen():
@@ -91,43 +172,32 @@ def test_shim_uses_only_declared_symbols():
         assert n_args == arity[m.group(1)], "%s called with %d arguments, declared with %d" % (m.group(1), n_args, arity[m.group(1)])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree is not on this box")
 def test_seam_patches_apply_to_the_reference():
     patches = sorted(f for f in os.listdir(os.path.join(RUST, "patches")) if f.endswith(".patch"))
     assert len(patches) == 5
-    with tempfile.TemporaryDirectory() as d:
-        for rel in ("src/optimized/split_dataframe/group/aggregation.rs", "src/optimized/split_dataframe/join.rs", "src/optimized/lazy.rs",
-                    "src/optimized/split_dataframe/group/types.rs", "src/optimized/split_dataframe/group/grouping.rs"):
-            os.makedirs(os.path.join(d, os.path.dirname(rel)), exist_ok=True)
-            shutil.copy(os.path.join("/root/reference", rel), os.path.join(d, rel))
-        for p in patches:
-            r = subprocess.run(["patch", "-p1", "-i", os.path.join(RUST, "patches", p)], cwd=d, capture_output=True, text=True)
-            assert r.returncode == 0, p + "\n" + r.stdout + r.stderr
-        # the patched sources call only what the shim defines, with the shim's arity
-        import re
-        shim = open(os.path.join(RUST, "hip_shim.rs")).read()
-        defined = {}
-        for m in re.finditer(r"pub fn (\w+)\s*\(", shim):
-            depth, i = 1, m.end()
-            while depth:
-                depth += {"(": 1, ")": -1}.get(shim[i], 0)
-                i += 1
-            defined[m.group(1)] = shim[m.end():i - 1]
-        for rel in ("group/aggregation.rs", "join.rs", "../lazy.rs", "group/grouping.rs"):
-            text = open(os.path.join(d, "src/optimized/split_dataframe", rel)).read()
-            for m in re.finditer(r"hip_shim::(\w+)\s*\(([^;{]*?)\)\s*[{)]", text, re.S):
-                name = m.group(1)
-                assert name in defined, name
-                if name != "hip_wanted":
-                    n_params = len(re.findall(r"\b\w+\s*:(?!:)", defined[name]))
-                    assert len([x for x in m.group(2).split(",") if x.strip()]) == n_params, (name, m.group(2))
-        # the braces of every patched file still balance
-        for rel in ("group/aggregation.rs", "join.rs", "../lazy.rs", "group/grouping.rs", "group/types.rs"):
-            text = open(os.path.join(d, "src/optimized/split_dataframe", rel)).read()
-            text = re.sub(r'"(?:[^"\\]|\\.)*"', '""', re.sub(r"//[^\n]*", "", text))
-            text = re.sub(r"'(?:[^'\\]|\\.)'", "' '", text)
-            for a, b in ("{}", "()", "[]"):
-                assert text.count(a) == text.count(b), (rel, a, text.count(a), text.count(b))
+    patched = _patched(_facts())
+    # the patched sources call only what the shim defines, with the shim's arity
+    shim = open(os.path.join(RUST, "hip_shim.rs")).read()
+    defined = {}
+    for m in re.finditer(r"pub fn (\w+)\s*\(", shim):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(shim[i], 0)
+            i += 1
+        defined[m.group(1)] = shim[m.end():i - 1]
+    for rel in ("group/aggregation.rs", "join.rs", "../lazy.rs", "group/grouping.rs"):
+        text = patched[os.path.normpath(os.path.join("src/optimized/split_dataframe", rel))][0]
+        for m in re.finditer(r"hip_shim::(\w+)\s*\(([^;{]*?)\)\s*[{)]", text, re.S):
+            name = m.group(1)
+            assert name in defined, name
+            if name != "hip_wanted":
+                n_params = len(re.findall(r"\b\w+\s*:(?!:)", defined[name]))
+                assert len([x for x in m.group(2).split(",") if x.strip()]) == n_params, (name, m.group(2))
+    # the braces of every patched file still balance
+    for rel in ("group/aggregation.rs", "join.rs", "../lazy.rs", "group/grouping.rs", "group/types.rs"):
+        counts = patched[os.path.normpath(os.path.join("src/optimized/split_dataframe", rel))][1]
+        for a, b in ("{}", "()", "[]"):
+            assert counts[a] == counts[b], (rel, a, counts[a], counts[b])
 
 
 # names after a '.' in hip_shim.rs that belong to std / core (everything else must exist in the reference crate)
@@ -140,7 +210,6 @@ _STD_MEMBERS = {
 }
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree is not on this box")
 def test_every_reference_member_the_shim_touches_exists():
     """hip_shim.rs cannot be compiled here.  Every `.name` it uses that is not a std / core method, and every
     `Type::name` path into the crate, must be declared in the reference sources (pub or pub(crate): the shim lives in
@@ -152,34 +221,30 @@ def test_every_reference_member_the_shim_touches_exists():
     own = set(re.findall(r"\bfn (\w+)", code)) | set(re.findall(r"^\s*(?:pub )?(\w+):", code, re.M))     # the shim's fns and struct fields
     ffi = open(os.path.join(RUST, "hip_ffi.rs")).read()
     own |= set(re.findall(r"pub (\w+):", ffi))
-    ref_files = ["src/column/int64_column.rs", "src/column/float64_column.rs", "src/column/string_column.rs", "src/column/boolean_column.rs",
-                 "src/column/string_pool.rs", "src/core/column.rs", "src/core/error.rs", "src/gpu/mod.rs",
-                 "src/optimized/split_dataframe/core.rs", "src/optimized/split_dataframe/column_ops.rs",
-                 "src/optimized/split_dataframe/data_ops.rs", "src/optimized/split_dataframe/group/types.rs",
-                 "src/optimized/split_dataframe/join.rs", "src/optimized/split_dataframe/index.rs", "src/index/multi_index.rs",
-                 "src/optimized/dataframe/core.rs", "src/optimized/dataframe/operations.rs"]
-    ref = "\n".join(open(os.path.join("/root/reference", f)).read() for f in ref_files)
-    declared = set(re.findall(r"\bfn (\w+)", ref)) | set(re.findall(r"pub(?:\(crate\))? (\w+):", ref))
+    facts = _facts()
+    declared = set(facts["declared"])          # fn names and pub / pub(crate) fields of the member files (make_reference_facts.py)
     used = set(re.findall(r"(?<![.\d])\.([A-Za-z_]\w*)\b", code)) - _STD_MEMBERS - own
     missing = sorted(n for n in used if n not in declared)
     assert not missing, "hip_shim.rs uses members the reference does not declare: %s" % missing
     for needed in ("indices", "optimization_mode", "columns", "column_indices", "filter_by_indices"):
         assert needed in used, needed
     # crate paths: modules re-export what the shim imports
-    for path, src, pat in [
-        ("crate::column::StringColumnOptimizationMode", "src/column/mod.rs", r"pub use string_column::\{[^}]*StringColumnOptimizationMode"),
-        ("crate::column::string_pool::GLOBAL_STRING_POOL", "src/column/string_pool.rs", r"pub static ref GLOBAL_STRING_POOL"),
-        ("crate::core::error::{Error, Result}", "src/core/error.rs", r"pub enum Error"),
-        ("crate::gpu::get_gpu_manager", "src/gpu/mod.rs", r"pub fn get_gpu_manager"),
-        ("StringColumnOptimizationMode::Legacy", "src/column/string_column.rs", r"\bLegacy,"),
-        ("crate::index::StringMultiIndex", "src/index/mod.rs", r"pub use (self::)?multi_index::\{[^}]*StringMultiIndex|pub use (self::)?multi_index::StringMultiIndex"),
-        ("crate::optimized::dataframe::OptimizedDataFrame", "src/optimized/mod.rs", r"pub use dataframe::\{[^}]*OptimizedDataFrame"),
-        ("crate::optimized::operations::AggregateOp", "src/optimized/operations.rs", r"pub enum AggregateOp"),
+    for path, src, name, origin in [
+        ("crate::column::StringColumnOptimizationMode", "src/column/mod.rs", "StringColumnOptimizationMode", "string_column"),
+        ("crate::index::StringMultiIndex", "src/index/mod.rs", "StringMultiIndex", "multi_index"),
+        ("crate::optimized::dataframe::OptimizedDataFrame", "src/optimized/mod.rs", "OptimizedDataFrame", "dataframe"),
     ]:
-        assert re.search(pat, open(os.path.join("/root/reference", src)).read()), path
+        assert origin in facts["pub_use"][src].get(name, []), path
+    for path, src, name in [
+        ("crate::column::string_pool::GLOBAL_STRING_POOL", "src/column/string_pool.rs", "GLOBAL_STRING_POOL"),
+        ("crate::core::error::{Error, Result}", "src/core/error.rs", "Error"),
+        ("crate::gpu::get_gpu_manager", "src/gpu/mod.rs", "get_gpu_manager"),
+        ("crate::optimized::operations::AggregateOp", "src/optimized/operations.rs", "AggregateOp"),
+    ]:
+        assert name in facts["pub_items"][src], path
+    assert "Legacy" in facts["enum_variants"]["StringColumnOptimizationMode"], "StringColumnOptimizationMode::Legacy"
     for variant in re.findall(r"Error::(\w+)\(", code):
-        assert re.search(r"\b%s\(String\)" % variant, open("/root/reference/src/core/error.rs").read()), variant
-
+        assert variant in facts["error_string_variants"], variant
 
 
 # ---- which TYPE does each patched call site hand to the shim? ---------------------------------------------------------
@@ -261,7 +326,6 @@ def test_import_resolver_reads_use_lines():
     assert _module_of("src/optimized/lazy.rs") == "crate::optimized::lazy"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree is not on this box")
 def test_patched_call_sites_pass_the_types_the_shim_is_typed_on():
     import re
     shim = open(os.path.join(RUST, "hip_shim.rs")).read()
@@ -273,28 +337,16 @@ def test_patched_call_sites_pass_the_types_the_shim_is_typed_on():
     assert sigs["groupby_aggregate_split_hip"] == {"OptimizedDataFrame": {split_frame},
                                                    "AggregateOp": {"crate::optimized::split_dataframe::group::types::AggregateOp"}}
     assert sigs["join_frame_split_hip"] == {"OptimizedDataFrame": {split_frame}, "JoinType": {"crate::optimized::split_dataframe::join::JoinType"}}
-    patches = sorted(f for f in os.listdir(os.path.join(RUST, "patches")) if f.endswith(".patch"))
     seen = set()
-    with tempfile.TemporaryDirectory() as d:
-        rels = ("src/optimized/split_dataframe/group/aggregation.rs", "src/optimized/split_dataframe/join.rs", "src/optimized/lazy.rs",
-                "src/optimized/split_dataframe/group/types.rs", "src/optimized/split_dataframe/group/grouping.rs")
-        for rel in rels:
-            os.makedirs(os.path.join(d, os.path.dirname(rel)), exist_ok=True)
-            shutil.copy(os.path.join("/root/reference", rel), os.path.join(d, rel))
-        for p in patches:
-            r = subprocess.run(["patch", "-p1", "-i", os.path.join(RUST, "patches", p)], cwd=d, capture_output=True, text=True)
-            assert r.returncode == 0, p + "\n" + r.stdout + r.stderr
-        for rel in rels:
-            text = open(os.path.join(d, rel)).read()
-            scope = _names_in_scope(text, _module_of(rel))
-            for m in re.finditer(r"hip_shim::(\w+)\s*\(", text):
-                name = m.group(1)
-                assert name in sigs, "%s calls hip_shim::%s, which the shim does not define as pub fn" % (rel, name)
-                seen.add(name)
-                for base, fulls in sigs[name].items():
-                    assert len(fulls) == 1, (name, base, fulls)
-                    assert base in scope, "%s calls hip_shim::%s (typed on %s) but has no %s in scope" % (rel, name, next(iter(fulls)), base)
-                    assert scope[base] in fulls, "%s: `%s` there is %s, but hip_shim::%s is typed on %s" % (rel, base, scope[base], name, next(iter(fulls)))
+    for rel, (text, _, scope) in sorted(_patched(_facts()).items()):
+        for m in re.finditer(r"hip_shim::(\w+)\s*\(", text):
+            name = m.group(1)
+            assert name in sigs, "%s calls hip_shim::%s, which the shim does not define as pub fn" % (rel, name)
+            seen.add(name)
+            for base, fulls in sigs[name].items():
+                assert len(fulls) == 1, (name, base, fulls)
+                assert base in scope, "%s calls hip_shim::%s (typed on %s) but has no %s in scope" % (rel, name, next(iter(fulls)), base)
+                assert scope[base] in fulls, "%s: `%s` there is %s, but hip_shim::%s is typed on %s" % (rel, base, scope[base], name, next(iter(fulls)))
     assert {"lazy_aggregate_hip", "lazy_join_groupby_sum_hip", "groupby_aggregate_split_hip", "join_frame_split_hip", "group_indices_hip",
             "par_groupby_hip"} <= seen, seen
 
