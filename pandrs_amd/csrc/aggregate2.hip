@@ -82,10 +82,14 @@ __global__ __launch_bounds__(AG_THREADS) void aggregate2_kernel(AggArgs a) {
         }
     };
     // SMALL: table b = rows [b * s_chunk, (b + 1) * s_chunk) of the original columns; no task list in memory
-    auto small_task = [&](uint32_t b) { return AggTask{0u, (uint32_t)min(b * a.s_chunk, a.s_rows), (uint32_t)min((b + 1) * a.s_chunk, a.s_rows), 0u}; };
+    // (64-bit until clamped to s_rows, as in clustered_kernel: (b + 1) * s_chunk may pass 2^32)
+    auto small_task = [&](uint32_t b) {
+        const uint64_t r0 = (uint64_t)b * a.s_chunk;
+        return AggTask{0u, (uint32_t)min(r0, (uint64_t)a.s_rows), (uint32_t)min(r0 + a.s_chunk, (uint64_t)a.s_rows), 0u};
+    };
     auto get_table = [&](uint32_t b) { return SMALL ? AggTable{b, 1u, 0u, 0u} : a.tables[a.order ? a.order[b] : b]; };
     auto get_task = [&](uint32_t i) { return SMALL ? small_task(i) : a.tasks[i]; };
-    const uint32_t n_tables = SMALL ? (a.s_rows + a.s_chunk - 1) / a.s_chunk : a.n_tasks[1];
+    const uint32_t n_tables = SMALL ? (uint32_t)(((uint64_t)a.s_rows + a.s_chunk - 1) / a.s_chunk) : a.n_tasks[1];
     uint32_t tb = blockIdx.x;
     if (tb >= n_tables) { finish(); return; }
     // the capacity-mode scatter dropped rows (its sampled regions were too small: rows clumped by position in a way the estimate's adjacent

@@ -73,7 +73,8 @@ __global__ __launch_bounds__(AG_THREADS) void clustered_kernel(AggArgs a) {
             }
         }
     };
-    const uint32_t n_chunks = PARTS ? a.n_tasks[1] : (a.s_rows + a.s_chunk - 1) / a.s_chunk;       // PARTS: the work list's tables
+    // (chunks: 64-bit, a chunk may be as long as the rows — s_rows + s_chunk passes 2^32 for a forced clustered_chunk)
+    const uint32_t n_chunks = PARTS ? a.n_tasks[1] : (uint32_t)(((uint64_t)a.s_rows + a.s_chunk - 1) / a.s_chunk);       // PARTS: the work list's tables
     uint32_t cb = blockIdx.x;
     if (cb >= n_chunks) { finish(); return; }
     if (resume && __hip_atomic_load(&a.counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { finish(); return; }      // launch 0 lost the attempt
@@ -128,7 +129,10 @@ __global__ __launch_bounds__(AG_THREADS) void clustered_kernel(AggArgs a) {
       for (uint32_t ti = 0; ti < tab.n_tasks; ti++) {          // the row ranges that feed this table (chunks: one)
         uint32_t r_beg, r_end;
         if (PARTS) { const AggTask tk = a.tasks[tab.task_beg + ti]; r_beg = tk.beg; r_end = tk.end; }
-        else { r_beg = cb * a.s_chunk; r_end = min(r_beg + a.s_chunk, a.s_rows); }
+        else {                 // 64-bit until clamped to s_rows: cb * s_chunk + s_chunk passes 2^32 near the per-call limit
+            const uint64_t b = (uint64_t)cb * a.s_chunk;
+            r_beg = (uint32_t)min(b, (uint64_t)a.s_rows); r_end = (uint32_t)min(b + a.s_chunk, (uint64_t)a.s_rows);
+        }
 
         // tiles of AG_THREADS x CL_R rows; no barrier inside a chunk: the waves drift apart and hide each other's loads
         // (PARTS: a range starts anywhere — the tiles start at the 64-byte boundary below it and the rows in front are masked)

@@ -54,7 +54,8 @@ static int32_t check_cols(const pandrs_hip_column *cols, int n, const char *what
 // ================================================================================================
 __global__ void zero_range_kernel(uint64_t *a, const uint32_t *beg, const uint32_t *end) {
     const uint32_t b = *beg, e = *end;
-    for (uint32_t i = b + blockIdx.x * blockDim.x + threadIdx.x; i < e; i += gridDim.x * blockDim.x) a[i] = 0ull;
+    // (64-bit: with e above 2^32 - 65536 a 32-bit i + stride wraps to a row in front of the range and the loop never ends)
+    for (uint64_t i = (uint64_t)b + blockIdx.x * blockDim.x + threadIdx.x; i < e; i += gridDim.x * blockDim.x) a[i] = 0ull;
 }
 __global__ void run_start_flags_kernel(const uint64_t *keys, const uint32_t *null_beg, uint32_t n, uint32_t *flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -887,7 +887,8 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     // rows per workgroup: every workgroup flushes its groups with global atomics, so more than ~64 of them cost more in
     // the flush than they gain in the stream (experiments/c1_chunks.py: 1 M rows / 1 K groups 59 us at 16 K rows per
     // workgroup, 79 us at 4 K; 100 K rows / 100 groups 40 us at 4 K, 46 us at 16 K)
-    const int64_t chunk = c->opt.small_chunk > 0 ? c->opt.small_chunk : std::max<int64_t>(4096, (N + 63) / 64);
+    const int64_t chunk = std::min<int64_t>(c->opt.small_chunk > 0 ? c->opt.small_chunk : std::max<int64_t>(4096, (N + 63) / 64),
+                                            (N + 1023) / 1024 * 1024);      // (longer than the rows = one chunk; s_chunk is 32-bit)
     aa.s_chunk = (uint32_t)((chunk + 1023) / 1024 * 1024);
     aa.g_slots = S; aa.g_keys = g_keys; aa.g_cnt = g_cnt; aa.g_states = g_states;
     aa.T = (uint32_t)T; aa.seed = 0x9E3779B9u; aa.n_src = n_src; aa.n_states = pl.n_states;
@@ -912,7 +913,7 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     volatile uint32_t *hp = reinterpret_cast<volatile uint32_t *>(c->pinned) + 1040;
     hp[4] = 0;
     aa.host_out = nullptr;                       // the fold publishes nothing: the output kernel does
-    const uint32_t n_tables = (aa.s_rows + aa.s_chunk - 1) / aa.s_chunk;
+    const uint32_t n_tables = (uint32_t)(((uint64_t)aa.s_rows + aa.s_chunk - 1) / aa.s_chunk);
     aa.launch_grid = n_tables;
     const size_t lds = (size_t)(T + 3) * slot_bytes + 192 + AGG2_LDS_EXTRA;
     // (no phase events: each one is a barrier packet between two 10-30 us kernels)
@@ -1209,6 +1210,8 @@ static int32_t run_clustered(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     chunk = std::min<int64_t>(chunk, std::max<int64_t>(N / (4 * (int64_t)std::max(c->n_cu, 1)), 16384));
     if (c->opt.clustered_chunk > 0) chunk = c->opt.clustered_chunk;
     chunk = std::max<int64_t>((chunk + 1023) / 1024 * 1024, 4096);
+    // (a chunk longer than the rows is one chunk: the same work, and a forced chunk of 2^32 rows or more must not truncate in s_chunk)
+    chunk = std::min<int64_t>(chunk, std::max<int64_t>((N + 1023) / 1024 * 1024, 4096));
     const int64_t n_tables = (N + chunk - 1) / chunk;
     const int64_t runs = (int64_t)((double)N * runs_per_row);
     const size_t dcap = (size_t)std::min<int64_t>(n_tables * (T + 2), 2 * runs + 2 * n_tables + 65536);

@@ -241,12 +241,15 @@ __global__ __launch_bounds__(JN_THREADS) void join_build_kernel(BuildArgs a) {
 // key with thousands of duplicates): the partitions were sorted by segmented_sort_u32; the sorted
 // non-null rows [0, *n_bound) form one array in which equal keys are adjacent (a key lives in
 // exactly one partition), so runs are published without looking at partition boundaries.
-__global__ void publish_runs_kernel(const uint64_t *rkeys, const uint32_t *rrows, const uint32_t *n_bound, TableRef tab) {
+// A run of 2^31 rows or more cannot be stored (bit 31 of JoinEntry.count is JN_DIRECT) and one thread would emit its pairs: it sets
+// *too_long and the host refuses the call.
+__global__ void publish_runs_kernel(const uint64_t *rkeys, const uint32_t *rrows, const uint32_t *n_bound, TableRef tab, uint32_t *too_long) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = *n_bound;
     if (i >= n) return;
     const uint64_t k = rkeys[i];
     if (i > 0 && rkeys[i - 1] == k) return;
     const uint32_t m = sorted_run_length(rkeys, i, n);
+    if (m & JN_DIRECT) { atomicOr(too_long, 1u); return; }
     const uint32_t e_start = m == 1 ? rrows[i] : i, e_count = m == 1 ? (1u | JN_DIRECT) : m;
     if (k == EMPTY_KEY) { tab.t[tab.sentinel()].start = e_start; tab.t[tab.sentinel()].count = e_count; return; }
     tab.insert(tab.base_of(k), k, e_start, e_count);
@@ -714,9 +717,19 @@ static int32_t join_core(pandrs_hip_ctx *c, const KeyDesc &lkey, int64_t nl, con
                 // a partition does not fit the LDS sort buffers (very many build rows, or one key with
                 // thousands of duplicates): general segmented sort, runs published from the sorted array
                 ST_TRY(segmented_sort_u32(c, prk, prr, rpart.offsets, rpart.NB, (uint32_t)P, nr));
-                if (nr > 0)
+                if (nr > 0) {
+                    uint32_t *too_long = c->work.take<uint32_t>(64);
+                    if (!too_long) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (join)");
+                    HIP_TRY(hipMemsetAsync(too_long, 0, 4, c->stream));
                     hipLaunchKernelGGL(publish_runs_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream,
-                                       prk, prr, rpart.offsets + (size_t)P * rpart.NB, tab);
+                                       prk, prr, rpart.offsets + (size_t)P * rpart.NB, tab, too_long);
+                    HIP_TRY(hipGetLastError());
+                    uint32_t h_too_long = 0;
+                    HIP_TRY(hipMemcpyAsync(&h_too_long, too_long, 4, hipMemcpyDeviceToHost, c->stream));
+                    HIP_TRY(hipStreamSynchronize(c->stream));
+                    if (h_too_long)
+                        return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "join: a right-side key has 2^31 rows or more (one run of the table holds fewer)");
+                }
             }
             HIP_TRY(hipGetLastError());
         }

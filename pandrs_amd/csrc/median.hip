@@ -60,7 +60,8 @@ __global__ __launch_bounds__(MC_THREADS) void compact_valid_kernel(KeyDesc key, 
 
 __global__ void fill_range_kernel(uint64_t *a, const uint32_t *beg, const uint32_t *end, uint64_t v) {
     const uint32_t b = *beg, e = *end;
-    for (uint32_t i = b + blockIdx.x * blockDim.x + threadIdx.x; i < e; i += gridDim.x * blockDim.x) a[i] = v;
+    // (64-bit: with e above 2^32 - 65536 a 32-bit i + stride wraps to a row in front of the range and the loop never ends)
+    for (uint64_t i = (uint64_t)b + blockIdx.x * blockDim.x + threadIdx.x; i < e; i += gridDim.x * blockDim.x) a[i] = v;
 }
 
 struct __attribute__((aligned(16))) MedianEntry {
