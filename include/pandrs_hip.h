@@ -205,6 +205,8 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *   "generic_aggregate" 1 = the descriptor-driven generic instantiation of the round-1 kernel
  *   "agg_depth"         register-ring depth of the lean aggregate (2..4; default 3)
  *   "agg_ablate"        experiments only: switch parts of the lean aggregate off (see experiments/agg2_ablate.py)
+ *   "sort_digit_bits"   experiments only: widest radix digit of pandrs_hip_sort_indices, 4 ... 11 (0 = the default, 11;
+ *                       experiments/sort_bench.py --digit-bits)
  *   "no_runs"           1 = never the clustered-rows (RUNS) instantiation
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
  *   "test_throw"        tests of the exception firewall (ctx may be NULL): 1 = the entry point's host code throws std::bad_alloc
@@ -457,6 +459,35 @@ int32_t pandrs_hip_join_groupby_sum(pandrs_hip_ctx *ctx, int32_t mem_space,
                                     const pandrs_hip_column *right_key,
                                     const pandrs_hip_column *right_group, int64_t n_right,
                                     int64_t *out_n_groups);
+
+/* ---- sort -------------------------------------------------------------------------------------------------
+ * OptimizedDataFrame::sort_by / sort_by_columns (src/optimized/split_dataframe/sort.rs:18-272, exposed on the public
+ * frame at src/optimized/dataframe/transformations.rs:1155-1230): out_idx[0 .. n_rows) = the STABLE permutation that
+ * orders the rows by keys[0], then keys[1], ... (sort.rs sorts with slice::sort_by, which is stable).
+ *   - ascending: n_keys flags (0 = descending), NULL = all ascending.  Descending inverts the comparison; rows that
+ *     compare equal on every key keep their original order in both directions.
+ *   - nulls sort LAST in both directions ((None, _) => Greater is applied before the direction); two nulls tie and
+ *     the comparison moves on to the next key.
+ *   - I64: signed order.  F64: numeric order, -0.0 == 0.0 (they tie).  BOOLBITS: false < true.
+ *   - U32CODE (string-pool codes) orders by the STRINGS, byte-wise (Rust String: Ord), not by code: code_rank[code]
+ *     is the position of the code's string in byte-wise order among the n_codes codes of the (global) pool.  One
+ *     table serves every string key.  It lives in mem_space, like the key columns; NULL, 0 when no key is a string.
+ *   - CELL64 is not a frame column type: PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ *   - documented deviation (NaN): the reference compares NaN as Equal to everything (partial_cmp(..).unwrap_or(
+ *     Equal)), which is not a total order: its result depends on the sort implementation.  Here NaN sorts after
+ *     every number and before nulls, in both directions, and NaNs tie among themselves.
+ * Errors: a U32CODE key without code_rank, or a code >= n_codes (checked on the device, no fault):
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; n_rows == 0:
+ * OK, nothing written; n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT; ctx NULL (no context could be created, e.g.
+ * no device): PANDRS_HIP_ERR_NOT_INITIALIZED.  The workspace (about 24 bytes per row, plus
+ * 8 per row for every further 64 bits of concatenated key codes) is sized up front: a memory_limit below it is
+ * PANDRS_HIP_ERR_OUT_OF_MEMORY.  Host key columns are staged; device / resident columns are read in place.  out_idx
+ * (n_rows int64 row indices, the element type of the gathers) lives in out_mem_space.  The frame a sort returns is
+ * select_rows_by_indices_impl (src/optimized/split_dataframe/select.rs:172-226): every column gathered through
+ * out_idx with nulls as 0 / 0.0 / "" / false and no null masks (pandrs_hip_gather_column). */
+int32_t pandrs_hip_sort_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
+                                const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
+                                int32_t out_mem_space, int64_t *out_idx);
 
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and

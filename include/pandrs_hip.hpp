@@ -5,7 +5,7 @@
 // the crate-side shim in a compiled language: same type and method names, argument meaning and error
 // behaviour as
 //   OptimizedDataFrame        src/optimized/split_dataframe/core.rs, group/grouping.rs:22-115,
-//                             join.rs:32-73, aggregate.rs:21-217
+//                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -39,7 +39,8 @@ namespace pandrs {
 
 // ---- errors (src/core/error.rs) ---------------------------------------------------------------------
 struct Error : std::runtime_error {
-    enum Kind { ColumnNotFound, ColumnTypeMismatch, OperationFailed, Computation, InvalidInput, DuplicateColumnName, InconsistentRowCount, Empty, Type, BelowThreshold, Index };
+    enum Kind { ColumnNotFound, ColumnTypeMismatch, OperationFailed, Computation, InvalidInput, DuplicateColumnName, InconsistentRowCount, Empty, Type, BelowThreshold, Index,
+                EmptyColumnList, InconsistentArrayLengths };   // the last two: sort.rs:147-149, :161-166
     Kind kind;
     Error(Kind k, const std::string &m) : std::runtime_error(m), kind(k) {}
 };
@@ -104,6 +105,16 @@ public:
     std::string get(uint32_t code) const {
         std::lock_guard<std::mutex> lock(mu_);
         return strings_.at(code);
+    }
+    // rank[code] = position of the code's string in byte-wise order (Rust String: Ord; std::string compares its
+    // chars as unsigned char): the table pandrs_hip_sort_indices orders string keys by
+    std::vector<uint32_t> rank_table() const {
+        std::lock_guard<std::mutex> lock(mu_);
+        std::vector<uint32_t> order(strings_.size()), rank(strings_.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return strings_[a] < strings_[b]; });
+        for (size_t i = 0; i < order.size(); i++) rank[order[i]] = (uint32_t)i;
+        return rank;
     }
 private:
     mutable std::mutex mu_;
@@ -184,6 +195,16 @@ struct ResidentSet {
     ResidentSet(const ResidentSet &) = delete;
     ResidentSet &operator=(const ResidentSet &) = delete;
     ~ResidentSet() { for (auto &c : cols) (void)pandrs_hip_column_release(context(), &c); }
+};
+// a host table copied to HBM for one call whose columns are resident (the string rank table of a sort), freed after it
+struct Staged {
+    pandrs_hip_column dev{};
+    const uint32_t *upload(const std::vector<uint32_t> &v) {
+        pandrs_hip_column host{v.data(), nullptr, PANDRS_HIP_U32CODE, 0};
+        check(pandrs_hip_column_upload(context(), &host, (int64_t)v.size(), &dev));
+        return static_cast<const uint32_t *>(dev.data);
+    }
+    ~Staged() { if (dev.data) (void)pandrs_hip_column_release(context(), &dev); }
 };
 // group-key cell -> the string the reference's result frame holds (grouping.rs:69-98)
 inline std::string key_string(int32_t dtype, uint64_t cell, bool is_null, const char *null_string = "NULL") {
@@ -272,6 +293,40 @@ public:
     double mean(const std::string &name) const { auto s = non_empty(name); return s.sum_f64 / (double)s.count; }
     double min(const std::string &name) const { return non_empty(name).min; }
     double max(const std::string &name) const { return non_empty(name).max; }
+
+    // sort.rs:18-143 / :146-272: the rows ordered by by[0], then by[1], ... (ascending: one flag per column, empty =
+    // all ascending).  Stable, also descending; nulls last in both directions; strings in byte-wise order; NaN after
+    // every number and before nulls (pandrs_hip.h).  The frame is select_rows_by_indices_impl's (select.rs:172-226):
+    // nulls become 0 / 0.0 / "" / false, no null masks, no columns when there are no rows.  The columns keep this
+    // frame's order (the reference emits them in HashMap order, which is unspecified).
+    OptimizedDataFrame sort_by(const std::string &by, bool ascending) const { return sort_by_columns({by}, {ascending}); }
+    OptimizedDataFrame sort_by_columns(const std::vector<std::string> &by, const std::vector<bool> &ascending = {}) const {
+        if (by.empty()) throw Error(Error::EmptyColumnList, "empty column list");
+        for (auto &name : by) if (!contains_column(name)) throw Error(Error::ColumnNotFound, name);
+        if (!ascending.empty() && ascending.size() != by.size())
+            throw Error(Error::InconsistentArrayLengths, "Inconsistent array lengths: expected " + std::to_string(by.size()) +
+                                                         ", found " + std::to_string(ascending.size()));
+        OptimizedDataFrame out;
+        if (row_count_ == 0) return out;
+        std::vector<pandrs_hip_column> keys;
+        std::vector<int32_t> asc;
+        bool strings = false;
+        for (size_t k = 0; k < by.size(); k++) {
+            keys.push_back(view_of(by[k]));
+            asc.push_back(ascending.empty() || ascending[k] ? 1 : 0);
+            strings = strings || keys.back().dtype == PANDRS_HIP_U32CODE;
+        }
+        std::vector<uint32_t> rank = strings ? StringPool::global().rank_table() : std::vector<uint32_t>{};
+        const uint32_t *rank_ptr = rank.data();
+        detail::Staged staged_rank;
+        if (strings && is_resident()) rank_ptr = staged_rank.upload(rank);     // one memory space per call
+        std::vector<int64_t> idx(row_count_);
+        detail::check(pandrs_hip_sort_indices(detail::context(), mem_space(), keys.data(), (int32_t)keys.size(), asc.data(),
+                                              strings ? rank_ptr : nullptr, (int64_t)rank.size(), (int64_t)row_count_,
+                                              PANDRS_HIP_MEM_HOST, idx.data()));
+        for (size_t c = 0; c < columns.size(); c++) out.add_column(column_names[c], gather(columns[c], idx));
+        return out;
+    }
 
     // data_ops.rs:124-209: row gather of every column; nulls become 0 / 0.0 / "" / false
     OptimizedDataFrame filter_by_indices(const std::vector<int64_t> &indices) const {

@@ -129,6 +129,8 @@ SYMBOLS = {
     "pandrs_hip_dist_join_groupby_sum": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(Column), C.POINTER(Column), C.c_int64,
                                                      C.POINTER(Column), C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64)]),
     "pandrs_hip_reduce_stats": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(ColumnStats)]),
+    "pandrs_hip_sort_indices": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int32, C.POINTER(C.c_int32), _P, C.c_int64,
+                                            C.c_int64, C.c_int32, _P]),
 }
 
 _lib = None

@@ -240,6 +240,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "deterministic")) c->opt.deterministic = value;
     else if (!std::strcmp(name, "exact_partition")) c->opt.exact_partition = value;
     else if (!std::strcmp(name, "agg_ablate")) c->opt.agg_ablate = value;
+    else if (!std::strcmp(name, "sort_digit_bits")) c->opt.sort_digit_bits = value;
     else if (!std::strcmp(name, "agg_depth")) c->opt.agg_depth = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
@@ -442,6 +443,14 @@ int32_t pandrs_hip_join_gather_key(pandrs_hip_ctx *ctx, int32_t src_mem_space, c
     if (!right_key) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_gather_key: null right key column");
     return pandrs::join_gather_entry(ctx, src_mem_space, left_key, n_left, 0, fill_bits, out_mem_space, out, right_key, n_right);
 } catch (...) { return pandrs::on_exception("pandrs_hip_join_gather_key"); }
+
+int32_t pandrs_hip_sort_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
+                                const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
+                                int32_t out_mem_space, int64_t *out_idx) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "sort_indices: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::sort_indices_entry(ctx, mem_space, keys, n_keys, ascending, code_rank, n_codes, n_rows, out_mem_space, out_idx);
+} catch (...) { return pandrs::on_exception("pandrs_hip_sort_indices"); }
 
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {

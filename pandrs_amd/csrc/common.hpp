@@ -221,6 +221,7 @@ struct Options {
     int64_t no_small = 0;            // 1 = never take the two-launch small-call path (groupby.hip run_small)
     int64_t agg_v1 = 0;              // 1 = never use the lean persistent aggregate kernel (aggregate2.hip)
     int64_t agg_depth = 0;           // experiments: register-ring depth of aggregate2 (C2 profile)
+    int64_t sort_digit_bits = 0;     // experiments: widest radix digit of pandrs_hip_sort_indices (0 = default, 4 ... 11)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
 
@@ -351,6 +352,9 @@ int32_t join_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pandrs
                           uint64_t fill_bits, int32_t out_mem_space, void *out, const pandrs_hip_column *key_right = nullptr, int64_t n_right = 0);
 int32_t gather_column_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *src, int64_t n_src,
                             const int64_t *idx, int64_t n, uint64_t fill_bits, void *out);
+int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
+                           const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
+                           int32_t out_mem_space, int64_t *out_idx);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

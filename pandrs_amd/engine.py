@@ -670,3 +670,36 @@ class Context:
         if st:
             _raise(st)
         return np.array(list(out)), cnt.value
+
+    # -- sort ----------------------------------------------------------------------------------------------
+    def sort_indices(self, keys, n_rows, ascending=None, code_rank=None):
+        """OptimizedDataFrame::sort_by_columns' row order (split_dataframe/sort.rs:18-272) on the device
+        (pandrs_hip_sort_indices): the stable permutation ordering the rows by keys[0], then keys[1], ...; nulls last
+        in both directions, NaN after every number and before nulls.  `keys` are (data, null_mask, dtype) triples
+        (host, device or ResidentColumn), `ascending` one flag per key (None = all ascending), `code_rank` the string
+        pool's rank table (rank[code] = position of the code's string in byte-wise order), needed when a key is a
+        string column.  -> int64 torch tensor of n_rows row indices on this context's device."""
+        import torch
+        keep = []
+        kc, sp = self._cols(keys, keep)
+        nk = len(keys)
+        asc = None
+        if ascending is not None:
+            asc = (C.c_int32 * max(nk, 1))(*[1 if a else 0 for a in ascending])
+        rank, n_codes = None, 0
+        if code_rank is not None:
+            if sp == L.MEM_DEVICE:
+                rank = code_rank if _is_torch(code_rank) else torch.from_numpy(
+                    np.ascontiguousarray(code_rank, dtype=np.uint32).view(np.int32)).to("cuda:%d" % self.device)
+                if _is_torch(code_rank):
+                    self._wait_for_producer()
+            else:
+                rank = np.ascontiguousarray(code_rank.cpu().numpy() if _is_torch(code_rank) else code_rank).view(np.uint32)
+            keep.append(rank)
+            n_codes = int(rank.numel() if _is_torch(rank) else rank.shape[0])
+        out = torch.empty(int(n_rows), dtype=torch.int64, device="cuda:%d" % self.device)
+        st = self.lib.pandrs_hip_sort_indices(self.h, sp, kc, nk, asc, _ptr(rank), n_codes, int(n_rows), L.MEM_DEVICE,
+                                              _ptr(out) if n_rows else None)
+        if st:
+            _raise(st)
+        return out

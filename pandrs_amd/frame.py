@@ -9,6 +9,7 @@ error behaviour — so the parity tests read like the reference's own tests.
   GroupBy.aggregate   src/optimized/split_dataframe/group/aggregation.rs:763  GroupBy.aggregate
   sum/mean/../agg     src/optimized/split_dataframe/group/operations.rs:438-521  GroupBy.sum ... GroupBy.agg
   *_join / join_impl  src/optimized/split_dataframe/join.rs:32-555    OptimizedDataFrame.inner_join ...
+  sort_by / sort_by_columns  src/optimized/split_dataframe/sort.rs:18-272  OptimizedDataFrame.sort_by / sort_by_columns
   LazyFrame           src/optimized/lazy.rs:98-170, :186-425          LazyFrame
   AggregateOp         src/optimized/split_dataframe/group/types.rs:11-34   AggregateOp
   JoinType            src/optimized/split_dataframe/join.rs:11-20     JoinType
@@ -52,6 +53,16 @@ class ColumnNotFound(KeyError):      # Error::ColumnNotFound (grouping.rs:55, jo
     pass
 
 
+class EmptyColumnList(ValueError):    # Error::EmptyColumnList (split_dataframe/sort.rs:147-149)
+    pass
+
+
+class InconsistentArrayLengths(ValueError):   # Error::InconsistentArrayLengths { expected, found } (sort.rs:161-166)
+    def __init__(self, expected, found):
+        super().__init__("Inconsistent array lengths: expected %d, found %d" % (expected, found))
+        self.expected, self.found = expected, found
+
+
 class DuplicateColumnName(ValueError):
     pass
 
@@ -84,6 +95,14 @@ class StringPool:
 
     def get(self, code):
         return self._strings[code]
+
+    def rank_table(self):
+        """rank[code] = position of the code's string in byte-wise order (Rust String: Ord).  UTF-8 byte order and
+        code-point order (Python str comparison) are the same order."""
+        order = sorted(range(len(self._strings)), key=self._strings.__getitem__)
+        rank = np.empty(len(order), np.uint32)
+        rank[np.asarray(order, dtype=np.int64)] = np.arange(len(order), dtype=np.uint32)
+        return rank
 
     def __len__(self):
         return len(self._strings)
@@ -360,6 +379,38 @@ class OptimizedDataFrame:
             result.add_column(name, g.take(self.column(name), left=True))
         return result
 
+    # -- sort (split_dataframe/sort.rs:18-272) --------------------------------------------------------------
+    def sort_by(self, by, ascending):
+        """sort.rs:18-143: the frame with its rows ordered by one column; see sort_by_columns."""
+        return self.sort_by_columns([by], [ascending])
+
+    def sort_by_columns(self, by, ascending=None):
+        """sort.rs:146-272: rows ordered by by[0], then by[1], ... (ascending: one flag per column, None = all
+        ascending).  Stable, also descending; nulls last in both directions; -0.0 ties 0.0; strings in byte-wise
+        order; NaN after every number and before nulls (the reference's NaN order is unspecified: pandrs_hip.h).
+        The result is select_rows_by_indices_impl's (select.rs:172-226): nulls become 0 / 0.0 / "" / false, no
+        null masks, and an empty frame has no columns.  The columns keep this frame's order (the reference emits
+        them in HashMap order, which is unspecified)."""
+        by = [by] if isinstance(by, str) else list(by)
+        if not by:
+            raise EmptyColumnList("empty column list")                      # sort.rs:147-149
+        for name in by:
+            if name not in self.column_indices:
+                raise ColumnNotFound(name)                                  # sort.rs:152-156
+        if ascending is not None and len(ascending) != len(by):
+            raise InconsistentArrayLengths(len(by), len(ascending))         # sort.rs:159-167
+        result = OptimizedDataFrame()
+        if self._row_count == 0:
+            return result                                                   # select.rs:177-179
+        cols = [self.column(name) for name in by]
+        rank = GLOBAL_STRING_POOL.rank_table() if any(c.dtype == L.U32CODE for c in cols) else None
+        ctx = get_context()
+        idx = ctx.sort_indices([c.view() for c in cols], self._row_count, ascending, rank)
+        g = _Gatherer(ctx, idx, idx)
+        for name in self.column_names:
+            result.add_column(name, g.take(self.column(name), left=True))
+        return result
+
     # -- whole-column reductions (K1: split_dataframe/aggregate.rs:21-215) ----------------------------------
     def _stats(self, name):
         col = self.column(name)
@@ -453,8 +504,8 @@ class _Gatherer:
         self.torch = torch
         self.ctx = ctx
         self.dev = "cuda:%d" % ctx.device
-        self.li = torch.from_numpy(np.ascontiguousarray(li)).to(self.dev)
-        self.ri = torch.from_numpy(np.ascontiguousarray(ri)).to(self.dev)
+        up = lambda a: a.to(self.dev) if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        self.li, self.ri = up(li), up(ri)
 
     def _up(self, a):
         if a is None:
