@@ -489,6 +489,37 @@ int32_t pandrs_hip_sort_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pa
                                 const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
                                 int32_t out_mem_space, int64_t *out_idx);
 
+/* ---- filter (stream compaction) ----------------------------------------------------------------------------
+ * OptimizedDataFrame::filter (src/optimized/split_dataframe/data_ops.rs:37-121), filter_rows (row_ops.rs:26-130),
+ * par_filter (parallel.rs:21-230) and select_by_mask (select.rs:150-167).  Two calls, in the shape of the join's retained
+ * pairs (pandrs_hip_join_indices -> pandrs_hip_join_gather):
+ *
+ * pandrs_hip_filter_indices: the selection.  cond is a BOOLBITS column of n_rows rows, with or without a null mask.  Row i is
+ * selected iff its value is Some(true) (the reference's `if let Ok(Some(true)) = bool_col.get(i)`): value bit set and
+ * null bit clear; a null row is never selected.  *out_count = the number of selected rows; out_idx (when not NULL) receives
+ * them as ascending int64 row indices, the element type every gather takes, in out_mem_space (room for *out_count
+ * elements; n_rows is always enough).  out_idx NULL = the count only.  The context keeps the selection (the condition
+ * as 64-bit words and one output offset per 4096-row tile) until the next pandrs_hip_filter_indices on it.
+ *
+ * pandrs_hip_filter_gather: one column compacted through the retained selection.  out (in out_mem_space) receives the
+ * selected rows' values in row order, *out_count of the last filter_indices elements: I64 / F64 as 8 bytes, U32CODE
+ * (string-pool codes) as 4, BOOLBITS as one 0 / 1 byte per row (as pandrs_hip_gather_column).  A null source cell becomes
+ * fill_bits (data_ops.rs writes 0 / 0.0 / String::new() / false: the caller passes 0, the bits of 0.0, the pool code of
+ * "" or 0), and the output has no null mask.  The source is streamed once; no index array is read.
+ *
+ * Both: host columns are staged; device / resident columns are read in place.
+ * Errors: ctx NULL (no context could be created, e.g. no device): PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than
+ * min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a condition that is not BOOLBITS: PANDRS_HIP_ERR_TYPE_MISMATCH
+ * (data_ops.rs:115 ColumnTypeMismatch); n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT; filter_gather with no retained
+ * selection, with n_src different from the selection's row count, or with a CELL64 column: PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ * n_rows == 0: OK, count 0 (a selection of 0 rows is retained).  The selection's workspace (n_rows / 8 bytes plus 8 bytes
+ * per 4096-row tile) is sized up front, as is the staging of host columns (their bytes, plus n_rows * 8 for a host out_idx,
+ * or the selected rows' bytes for a host out): a memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY. */
+int32_t pandrs_hip_filter_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cond, int64_t n_rows,
+                                  int32_t out_mem_space, int64_t *out_idx, int64_t *out_count);
+int32_t pandrs_hip_filter_gather(pandrs_hip_ctx *ctx, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src,
+                                 uint64_t fill_bits, int32_t out_mem_space, void *out);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

@@ -5,7 +5,8 @@
 // the crate-side shim in a compiled language: same type and method names, argument meaning and error
 // behaviour as
 //   OptimizedDataFrame        src/optimized/split_dataframe/core.rs, group/grouping.rs:22-115,
-//                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272
+//                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272, data_ops.rs:15-121,
+//                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -40,7 +41,8 @@ namespace pandrs {
 // ---- errors (src/core/error.rs) ---------------------------------------------------------------------
 struct Error : std::runtime_error {
     enum Kind { ColumnNotFound, ColumnTypeMismatch, OperationFailed, Computation, InvalidInput, DuplicateColumnName, InconsistentRowCount, Empty, Type, BelowThreshold, Index,
-                EmptyColumnList, InconsistentArrayLengths };   // the last two: sort.rs:147-149, :161-166
+                EmptyColumnList, InconsistentArrayLengths,     // sort.rs:147-149, :161-166
+                Format };                                      // select.rs:151-157 (select_by_mask's mask length)
     Kind kind;
     Error(Kind k, const std::string &m) : std::runtime_error(m), kind(k) {}
 };
@@ -337,9 +339,84 @@ public:
         return out;
     }
 
+    // data_ops.rs:15-34: the named columns, in the order given, null masks kept; host only
+    OptimizedDataFrame select(const std::vector<std::string> &names) const {
+        OptimizedDataFrame out;
+        for (auto &name : names) out.add_column(name, column(name));
+        return out;
+    }
+    // data_ops.rs:37-121 (filter_rows, row_ops.rs:26-130, is the same body): the rows whose Boolean condition is
+    // Some(true), in order; nulls become 0 / 0.0 / "" / false and there are no masks; no selected row keeps every
+    // column with 0 rows.  Missing column: ColumnNotFound; not Boolean: ColumnTypeMismatch (data_ops.rs:115).
+    OptimizedDataFrame filter(const std::string &condition_column) const {
+        const pandrs_hip_column cond = condition(condition_column);
+        if (row_count_ == 0) return empty_columns();
+        return compact(cond, mem_space()).first;
+    }
+    OptimizedDataFrame filter_rows(const std::string &condition_column) const { return filter(condition_column); }
+    // parallel.rs:21-230: filter's rows; no selected row: explicitly empty typed columns (parallel.rs:73-90)
+    OptimizedDataFrame par_filter(const std::string &condition_column) const {
+        const pandrs_hip_column cond = condition(condition_column);
+        if (row_count_ == 0) return empty_columns();
+        auto r = compact(cond, mem_space());
+        return r.second ? std::move(r.first) : empty_columns();
+    }
+    // select.rs:150-167 through select_rows_by_indices_impl (:172-226): no selected row is a frame with NO columns; a
+    // mask of the wrong length is Error::Format.  The mask is packed to bits and filtered on the device.  The columns
+    // keep this frame's order (the reference emits them in HashMap order, which is unspecified).
+    OptimizedDataFrame select_by_mask(const std::vector<bool> &mask) const {
+        if (mask.size() != row_count_)
+            throw Error(Error::Format, "Mask length (" + std::to_string(mask.size()) + ") does not match DataFrame row count (" +
+                                       std::to_string(row_count_) + ")");
+        if (row_count_ == 0 || columns.empty()) return OptimizedDataFrame();
+        const BooleanColumn bits(mask);
+        auto r = compact(pandrs_hip_column{bits.bits.data(), nullptr, PANDRS_HIP_BOOLBITS, 0}, PANDRS_HIP_MEM_HOST);
+        return r.second ? std::move(r.first) : OptimizedDataFrame();
+    }
+
 private:
     size_t row_count_ = 0;
     std::shared_ptr<detail::ResidentSet> resident_;
+
+    pandrs_hip_column condition(const std::string &name) const {
+        const Column &c = column(name);
+        if (c.index() != 3)
+            throw Error(Error::ColumnTypeMismatch, "Column type mismatch: column '" + name + "' expected Boolean");
+        return view_of(name);
+    }
+    OptimizedDataFrame empty_columns() const {
+        OptimizedDataFrame out;
+        for (size_t c = 0; c < columns.size(); c++)
+            out.add_column(column_names[c], std::visit([](auto &x) -> Column { return std::decay_t<decltype(x)>(); }, columns[c]));
+        return out;
+    }
+    // one selection (pandrs_hip_filter_indices), then every column compacted through it (pandrs_hip_filter_gather); the
+    // condition's memory space is its own (select_by_mask's mask is on the host while the columns may be resident)
+    std::pair<OptimizedDataFrame, int64_t> compact(const pandrs_hip_column &cond, int32_t cond_space) const {
+        int64_t n = 0;
+        detail::check(pandrs_hip_filter_indices(detail::context(), cond_space, &cond, (int64_t)row_count_, PANDRS_HIP_MEM_HOST, nullptr, &n));
+        OptimizedDataFrame out;
+        for (size_t c = 0; c < columns.size(); c++) {
+            const Column &src = columns[c];
+            pandrs_hip_column v = view_of(column_names[c]);
+            auto call = [&](uint64_t fill, void *o) {
+                detail::check(pandrs_hip_filter_gather(detail::context(), mem_space(), &v, (int64_t)row_count_, fill, PANDRS_HIP_MEM_HOST, o));
+            };
+            switch (src.index()) {
+            case 0: { Int64Column o; o.data.resize(n); call(0, o.data.data()); out.add_column(column_names[c], std::move(o)); break; }
+            case 1: { Float64Column o; o.data.resize(n); call(0, o.data.data()); out.add_column(column_names[c], std::move(o)); break; }
+            case 2: { StringColumn o; o.indices.resize(n); call(StringPool::global().get_or_insert(""), o.indices.data()); out.add_column(column_names[c], std::move(o)); break; }
+            default: {
+                std::vector<uint8_t> bytes(n);
+                call(0, bytes.data());
+                std::vector<bool> b(n);
+                for (int64_t i = 0; i < n; i++) b[i] = bytes[i] != 0;
+                out.add_column(column_names[c], BooleanColumn(b));
+            }
+            }
+        }
+        return {std::move(out), n};
+    }
 
     pandrs_hip_column_stats stats(const std::string &name) const {
         const Column &c = column(name);

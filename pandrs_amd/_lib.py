@@ -131,6 +131,8 @@ SYMBOLS = {
     "pandrs_hip_reduce_stats": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(ColumnStats)]),
     "pandrs_hip_sort_indices": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int32, C.POINTER(C.c_int32), _P, C.c_int64,
                                             C.c_int64, C.c_int32, _P]),
+    "pandrs_hip_filter_indices": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
+    "pandrs_hip_filter_gather": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_uint64, C.c_int32, _P]),
 }
 
 _lib = None

@@ -98,7 +98,7 @@ int32_t pandrs_hip_ctx_destroy(pandrs_hip_ctx *c) try {
     if (!c) return PANDRS_HIP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release();
+    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release();
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) { (void)hipEventDestroy(c->ev_begin[i]); (void)hipEventDestroy(c->ev_end[i]); }
     (void)hipEventDestroy(c->ev_call_begin); (void)hipEventDestroy(c->ev_call_end);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -451,6 +451,20 @@ int32_t pandrs_hip_sort_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pa
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::sort_indices_entry(ctx, mem_space, keys, n_keys, ascending, code_rank, n_codes, n_rows, out_mem_space, out_idx);
 } catch (...) { return pandrs::on_exception("pandrs_hip_sort_indices"); }
+
+int32_t pandrs_hip_filter_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cond, int64_t n_rows,
+                                  int32_t out_mem_space, int64_t *out_idx, int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "filter_indices: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::filter_indices_entry(ctx, mem_space, cond, n_rows, out_mem_space, out_idx, out_count);
+} catch (...) { return pandrs::on_exception("pandrs_hip_filter_indices"); }
+
+int32_t pandrs_hip_filter_gather(pandrs_hip_ctx *ctx, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src,
+                                 uint64_t fill_bits, int32_t out_mem_space, void *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "filter_gather: no context");
+    ST_TRY(pandrs::below_threshold(n_src));
+    return pandrs::filter_gather_entry(ctx, src_mem_space, src, n_src, fill_bits, out_mem_space, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_filter_gather"); }
 
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {

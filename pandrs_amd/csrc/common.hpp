@@ -173,6 +173,15 @@ struct JoinResult {
     int64_t *left_idx = nullptr, *right_idx = nullptr;
 };
 
+// the selection of the last pandrs_hip_filter_indices (filter.hip): sel = condition & ~null as 64-bit words, and every
+// 4096-row tile's output offset (offs[n_tiles] = the selected row count); pandrs_hip_filter_gather compacts through it
+struct FilterResult {
+    bool valid = false;
+    int64_t n_rows = 0, n_tiles = 0, n_selected = 0;
+    uint64_t *sel = nullptr;     // [(n_rows + 63) / 64]
+    uint32_t *offs = nullptr;    // [n_tiles + 1]
+};
+
 struct Options {
     int64_t groups_hint = 0;     // 0 = estimate from a sample
     int64_t scatter_staged = 1;  // stage columns through LDS for coalesced partition writes
@@ -236,12 +245,14 @@ struct pandrs_hip_ctx {
     // side: slice records; super: two-level columns; packed: multi-key cells and dictionaries;
     // pairs: fused-join pairs; groups: retained group index (CSR); shuf: retained shuffle buckets)
     pandrs::Arena work, result, staging, temp, result2, result3, side, super, packed, pairs, groups, shuf, absorb, overflow;
+    pandrs::Arena filt;          // the retained filter selection (filter.hip)
     pandrs::Options opt;
     pandrs_hip_timings timings{};
     pandrs::GroupbyResult gb, gb2, gb3;   // gb2 / gb3: nested results (slice merges, two-level sub-runs)
     pandrs::JoinResult jn;
     pandrs::GroupsResult gr;
     pandrs::ShuffleResult sh;
+    pandrs::FilterResult fl;
     // phase timing: pairs of events
     hipEvent_t ev_begin[PANDRS_HIP_MAX_PHASES]{}, ev_end[PANDRS_HIP_MAX_PHASES]{};
     bool ev_used[PANDRS_HIP_MAX_PHASES]{};
@@ -355,6 +366,11 @@ int32_t gather_column_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
 int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
                            const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
                            int32_t out_mem_space, int64_t *out_idx);
+int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *cond, int64_t n_rows,
+                             int32_t out_mem_space, int64_t *out_idx, int64_t *out_count);
+int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src, uint64_t fill_bits,
+                            int32_t out_mem_space, void *out);
+size_t filter_workspace_bytes(int64_t n_rows);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

@@ -703,3 +703,42 @@ class Context:
         if st:
             _raise(st)
         return out
+
+    # -- filter (stream compaction) ---------------------------------------------------------------------------
+    def filter_indices(self, cond, n_rows, indices=True):
+        """OptimizedDataFrame::filter's selection (split_dataframe/data_ops.rs:37-121) on the device
+        (pandrs_hip_filter_indices): the rows whose BOOLBITS condition is Some(true), ascending.  `cond` is a
+        (bits, null_mask, dtype) triple (host, device or ResidentColumn).  The context keeps the selection for
+        filter_gather until the next filter_indices.  -> (int64 torch tensor of the selected rows on this context's
+        device, or None when indices=False, selected row count)."""
+        import torch
+        keep = []
+        cc, sp = self._cols([tuple(cond)], keep)
+        out = torch.empty(max(int(n_rows), 1), dtype=torch.int64, device="cuda:%d" % self.device) if indices else None
+        cnt = C.c_int64(0)
+        st = self.lib.pandrs_hip_filter_indices(self.h, sp, cc, int(n_rows), L.MEM_DEVICE, _ptr(out), C.byref(cnt))
+        if st:
+            _raise(st)
+        return (out[:cnt.value] if indices else None), cnt.value
+
+    def filter_gather(self, col, n_src, n_out, fill=0, out_device=False):
+        """One column compacted through the selection of the last filter_indices (pandrs_hip_filter_gather): the
+        selected rows' values in row order, nulls as `fill`, no mask.  `col` is a (data, mask, dtype) triple on the
+        host or the device, or a ResidentColumn; n_out = the selection's count.  -> numpy array of n_out elements
+        (uint8 per row for BOOLBITS sources), or with out_device a torch tensor on this context's device (int32 for
+        U32CODE)."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        dtype = tuple(col)[2]
+        if out_device:
+            import torch
+            out = torch.empty(int(n_out), dtype={L.I64: torch.int64, L.F64: torch.float64, L.U32CODE: torch.int32,
+                                                 L.BOOLBITS: torch.uint8}.get(dtype, torch.int64), device="cuda:%d" % self.device)
+        else:
+            out = np.empty(int(n_out), {L.F64: np.float64, L.U32CODE: np.uint32, L.BOOLBITS: np.uint8}.get(dtype, np.int64))
+        fill_bits = int(np.float64(fill).view(np.uint64)) if dtype == L.F64 else int(fill) & 0xFFFFFFFFFFFFFFFF
+        st = self.lib.pandrs_hip_filter_gather(self.h, sp, cc, int(n_src), fill_bits, L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                               _ptr(out) if int(n_out) else None)
+        if st:
+            _raise(st)
+        return out

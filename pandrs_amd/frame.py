@@ -10,6 +10,10 @@ error behaviour — so the parity tests read like the reference's own tests.
   sum/mean/../agg     src/optimized/split_dataframe/group/operations.rs:438-521  GroupBy.sum ... GroupBy.agg
   *_join / join_impl  src/optimized/split_dataframe/join.rs:32-555    OptimizedDataFrame.inner_join ...
   sort_by / sort_by_columns  src/optimized/split_dataframe/sort.rs:18-272  OptimizedDataFrame.sort_by / sort_by_columns
+  select / filter     src/optimized/split_dataframe/data_ops.rs:15-121    OptimizedDataFrame.select / filter
+  filter_rows         src/optimized/split_dataframe/row_ops.rs:26-130     OptimizedDataFrame.filter_rows
+  par_filter          src/optimized/split_dataframe/parallel.rs:21-230    OptimizedDataFrame.par_filter
+  select_by_mask      src/optimized/split_dataframe/select.rs:150-167     OptimizedDataFrame.select_by_mask
   LazyFrame           src/optimized/lazy.rs:98-170, :186-425          LazyFrame
   AggregateOp         src/optimized/split_dataframe/group/types.rs:11-34   AggregateOp
   JoinType            src/optimized/split_dataframe/join.rs:11-20     JoinType
@@ -61,6 +65,10 @@ class InconsistentArrayLengths(ValueError):   # Error::InconsistentArrayLengths 
     def __init__(self, expected, found):
         super().__init__("Inconsistent array lengths: expected %d, found %d" % (expected, found))
         self.expected, self.found = expected, found
+
+
+class FormatError(ValueError):        # Error::Format (select.rs:151-157: a mask whose length is not the row count)
+    pass
 
 
 class DuplicateColumnName(ValueError):
@@ -409,6 +417,78 @@ class OptimizedDataFrame:
         g = _Gatherer(ctx, idx, idx)
         for name in self.column_names:
             result.add_column(name, g.take(self.column(name), left=True))
+        return result
+
+    # -- select / filter (data_ops.rs:15-121, row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167) ----------
+    def select(self, columns):
+        """data_ops.rs:15-34: a frame of the named columns, in the order given, shared as they are (null masks kept).
+        A missing name is ColumnNotFound; a repeated one DuplicateColumnName (add_column).  Host only."""
+        result = OptimizedDataFrame()
+        for name in ([columns] if isinstance(columns, str) else columns):
+            result.add_column(name, self.column(name))
+        return result
+
+    def _condition(self, condition_column):
+        if condition_column not in self.column_indices:
+            raise ColumnNotFound(condition_column)                       # data_ops.rs:39-42
+        cond = self.column(condition_column)
+        if cond.dtype != L.BOOLBITS:                                     # data_ops.rs:115-119
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column type mismatch: column '%s' expected Boolean, found %s"
+                                     % (condition_column, cond.column_type()))
+        return cond
+
+    def _compact(self, cond_view):
+        """Every column compacted on the device through one selection (pandrs_hip_filter_indices, then
+        pandrs_hip_filter_gather per column): nulls become 0 / 0.0 / "" / false, no masks.  -> (frame, count)."""
+        ctx = get_context()
+        _, count = ctx.filter_indices(cond_view, self._row_count, indices=False)
+        result = OptimizedDataFrame()
+        for name in self.column_names:
+            col = self.column(name)
+            fill = GLOBAL_STRING_POOL.get_or_insert("") if col.dtype == L.U32CODE else 0
+            result.add_column(name, _Gatherer._wrap(col, ctx.filter_gather(col.view(), self._row_count, count, fill)))
+        return result, count
+
+    def filter(self, condition_column):
+        """data_ops.rs:37-121: the rows whose Boolean condition is Some(true), in order (a null condition drops the row).
+        Every column is kept; nulls become 0 / 0.0 / "" / false and the result has no masks.  No selected row: every
+        column with 0 rows.  A missing column is ColumnNotFound, a non-Boolean one ColumnTypeMismatch."""
+        cond = self._condition(condition_column)
+        if self._row_count == 0:
+            return self._empty_columns()
+        return self._compact(cond.view())[0]
+
+    def filter_rows(self, condition_column):
+        """row_ops.rs:26-130: filter's body again (the same rows, defaults and empty shape; the frame has no index here)."""
+        return self.filter(condition_column)
+
+    def par_filter(self, condition_column):
+        """parallel.rs:21-230: the same rows as filter.  No selected row: explicitly empty typed columns, one per column
+        (parallel.rs:73-90), which is filter's shape too.  The reference's serial / parallel split (100 000 rows)
+        changes only how the host loops run; here every size takes the device."""
+        cond = self._condition(condition_column)
+        if self._row_count == 0:
+            return self._empty_columns()
+        result, count = self._compact(cond.view())
+        return result if count else self._empty_columns()
+
+    def select_by_mask(self, mask):
+        """select.rs:150-167: the rows where mask is true, through select_rows_by_indices_impl (select.rs:172-226):
+        nulls become defaults, no masks, and no selected row is a frame with NO columns.  A mask whose length is not the
+        row count is Error::Format (FormatError).  The mask is packed to bits and filtered on the device.  The columns
+        keep this frame's order (the reference emits them in HashMap order, which is unspecified)."""
+        mask = np.asarray(mask, dtype=bool).reshape(-1)
+        if mask.shape[0] != self._row_count:
+            raise FormatError("Mask length (%d) does not match DataFrame row count (%d)" % (mask.shape[0], self._row_count))
+        if self._row_count == 0 or not self.columns:
+            return OptimizedDataFrame()                                  # select.rs:177-179
+        result, count = self._compact((np.packbits(mask, bitorder="little"), None, L.BOOLBITS))
+        return result if count else OptimizedDataFrame()
+
+    def _empty_columns(self):
+        result = OptimizedDataFrame()
+        for name in self.column_names:
+            result.add_column(name, _empty_like(self.column(name)))
         return result
 
     # -- whole-column reductions (K1: split_dataframe/aggregate.rs:21-215) ----------------------------------
@@ -785,7 +865,10 @@ class GroupBy:
 
 # ---------------------------------------------------------------------------------------------- LazyFrame
 class LazyFrame:
-    """LazyFrame (lazy.rs:98-170): only the two operations on the hot path are mirrored."""
+    """LazyFrame (lazy.rs:98-170): the Select, Filter, Aggregate and Join arms, executed in plan order (lazy.rs:172-425).
+    Select is OptimizedDataFrame.select, Filter is par_filter (lazy.rs:175-182).  The Map and Sort arms are not mirrored:
+    the reference's Sort arm (lazy.rs:426-...) orders rows by each value's formatted string (so 10 sorts before 9),
+    which is a separate piece of work."""
 
     def __init__(self, df):
         self.source = df
@@ -794,6 +877,14 @@ class LazyFrame:
     @classmethod
     def new(cls, df):
         return cls(df)
+
+    def select(self, columns):
+        self.operations.append(("select", [columns] if isinstance(columns, str) else list(columns)))
+        return self
+
+    def filter(self, condition):
+        self.operations.append(("filter", condition))
+        return self
 
     def aggregate(self, group_by, aggregations):
         self.operations.append(("aggregate", list(group_by), list(aggregations)))
@@ -810,7 +901,11 @@ class LazyFrame:
         while i < len(ops):
             op = ops[i]
             i += 1
-            if op[0] == "aggregate":
+            if op[0] == "select":
+                df = df.select(op[1])                                 # lazy.rs:175-178
+            elif op[0] == "filter":
+                df = df.par_filter(op[1])                             # lazy.rs:179-182
+            elif op[0] == "aggregate":
                 _, group_by, aggregations = op
                 for _, agg_op, _ in aggregations:             # lazy.rs:377-382: only these five ops
                     if AggregateOp(int(agg_op)) not in (AggregateOp.Sum, AggregateOp.Mean, AggregateOp.Min,
