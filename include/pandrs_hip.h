@@ -520,6 +520,77 @@ int32_t pandrs_hip_filter_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const 
 int32_t pandrs_hip_filter_gather(pandrs_hip_ctx *ctx, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src,
                                  uint64_t fill_bits, int32_t out_mem_space, void *out);
 
+/* ---- window statistics (rolling / expanding / EWM) -----------------------------------------------------------------
+ * DataFrameWindowExt::{rolling, expanding, ewm} (src/dataframe/window.rs:13-160) over src/series/window.rs: Rolling
+ * (:163-200 bounds, ops :206-345), Expanding (:379-400, ops :404-500), EWM (:608 get_alpha, :640-724).
+ *
+ * pandrs_hip_window: one statistic of one numeric column of n_rows rows.  col is I64 (cells `as f64`) or F64, with or
+ * without a null mask (a null cell is the reference's None).  out (in out_mem_space) receives n_rows doubles; NaN marks a
+ * None, and count is written as f64 (enhanced_window.rs).  The spec:
+ *   kind  ROLLING: row i covers [max(0, i+1-window), i+1); center = 1: start = i >= window/2 ? i - window/2 : 0,
+ *                  end = min(start + window, n) (so the first windows are [0, window), not a symmetric cut).
+ *                  window >= 1 (window.rs:112-117); min_periods < 0 means window (:146).
+ *         EXPANDING: row i covers [0, i+1); min_periods >= 0, taken as given (0 allowed).
+ *         EWM:   alpha resolved by the caller (get_alpha, :608: alpha, 2/(span+1) or 1 - exp(-ln2/halflife)); it must be
+ *                finite; adjust / ignore_na / ddof are never read by the reference and are not part of the spec.
+ *   op    SUM / MEAN / VAR / STD / MIN / MAX / COUNT for ROLLING and EXPANDING; MEAN / STD / VAR for EWM.
+ * Rolling and expanding: the window's values are its non-null cells in row order; fewer than min_periods -> NaN (count:
+ * 0).  Otherwise sum = the left fold from -0.0 (current Rust std's `Sum for f64`), mean = sum / len, var = NaN when
+ * len <= ddof, else mean as above and sum of (x-mean)*(x-mean) in row order / (len-ddof), std = sqrt(var),
+ * min / max = fold(+-INFINITY, f64::min / max) (NaN cells ignored, a window of only NaN gives +-inf), count = len.
+ * EWM mean: NaN until the first non-null value, which is output as itself, then y = alpha*v + (1-alpha)*y; a null row
+ * repeats y.  EWM std: NaN up to and including the first value, then with diff = v - mean_prev,
+ * var = (1-alpha)*(var + alpha*diff*diff), output sqrt(var); a null row repeats it.  EWM var = the std output squared
+ * (:715-724, not the internal var).
+ *
+ * Parity.  Bit for bit: rolling sum / mean / var / std at every window (the same fold, in the same
+ * order, no contraction; sqrt and f64 division are correctly rounded on the device), rolling and expanding min / max /
+ * count, EWM rows before the first carried-in value.  Deviations:
+ *  - min / max over values mixing +0.0 and -0.0: -0.0 < +0.0 (IEEE total order); f64::min leaves that tie unspecified;
+ *  - expanding sum / mean: a compensated (double-double) parallel prefix, within 1e-9 * sum|x| of the row-order prefix
+ *    (the sign of a zero sum is kept: a window of only -0.0, or an empty one under min_periods 0, sums to -0.0);
+ *  - expanding var / std: Chan et al.'s merge of (count, mean, M2), within 1e-9 relative of the two-pass restatement,
+ *    with an absolute floor of 1e-12 * max|x|^2 for var (1e-6 * max|x| for std) over the rows so far;
+ *  - EWM mean / std / var: affine scans, then each thread re-runs the reference's recurrence from its carried-in value;
+ *    within 1e-12 * max|x| over the rows so far (var, the std output squared: 2e-12 * max|x|^2).
+ * Host columns are staged; device and resident columns are read in place (data 8-byte aligned; a null mask at any byte
+ * offset).  Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold:
+ * PANDRS_HIP_ERR_BELOW_THRESHOLD; a column that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a bad spec (kind, op for
+ * the kind, window < 1, center not 0 / 1, ddof < 0, expanding min_periods < 0, a non-finite alpha) or n_rows >= 2^32:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written.  Workspace is sized up front (rolling min / max /
+ * count: 16 bytes per row, + 8 with a null mask; EWM std / var: 1 byte per row; staging: the host column and out): a
+ * memory_limit below it is PANDRS_HIP_ERR_OUT_OF_MEMORY.  Out of scope: median, quantile and apply (series/window.rs),
+ * the `closed` option (accepted by the reference, never read). */
+typedef enum pandrs_hip_window_kind {
+    PANDRS_HIP_WINDOW_KIND_ROLLING = 0,
+    PANDRS_HIP_WINDOW_KIND_EXPANDING = 1,
+    PANDRS_HIP_WINDOW_KIND_EWM = 2
+} pandrs_hip_window_kind;
+
+typedef enum pandrs_hip_window_op {
+    PANDRS_HIP_WINDOW_SUM = 0,
+    PANDRS_HIP_WINDOW_MEAN = 1,
+    PANDRS_HIP_WINDOW_VAR = 2,
+    PANDRS_HIP_WINDOW_STD = 3,
+    PANDRS_HIP_WINDOW_MIN = 4,
+    PANDRS_HIP_WINDOW_MAX = 5,
+    PANDRS_HIP_WINDOW_COUNT = 6
+} pandrs_hip_window_op;
+
+typedef struct pandrs_hip_window_spec {
+    int32_t kind;           /* pandrs_hip_window_kind */
+    int32_t op;             /* pandrs_hip_window_op */
+    int64_t window;         /* ROLLING: window_size >= 1 */
+    int64_t min_periods;    /* ROLLING: < 0 = window; EXPANDING: >= 0 */
+    int32_t center;         /* ROLLING: 0 / 1 */
+    int32_t reserved;
+    int64_t ddof;           /* VAR / STD of ROLLING and EXPANDING: >= 0 */
+    double alpha;           /* EWM */
+} pandrs_hip_window_spec;
+
+int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                          const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

@@ -6,7 +6,8 @@
 // behaviour as
 //   OptimizedDataFrame        src/optimized/split_dataframe/core.rs, group/grouping.rs:22-115,
 //                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272, data_ops.rs:15-121,
-//                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167
+//                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167;
+//                             rolling / expanding / ewm: src/dataframe/window.rs:13-160 (series/window.rs)
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -18,6 +19,7 @@
 // reference's own tests through it.
 #pragma once
 #include <algorithm>
+#include <cctype>
 #include <charconv>
 #include <cmath>
 #include <cstdint>
@@ -42,7 +44,8 @@ namespace pandrs {
 struct Error : std::runtime_error {
     enum Kind { ColumnNotFound, ColumnTypeMismatch, OperationFailed, Computation, InvalidInput, DuplicateColumnName, InconsistentRowCount, Empty, Type, BelowThreshold, Index,
                 EmptyColumnList, InconsistentArrayLengths,     // sort.rs:147-149, :161-166
-                Format };                                      // select.rs:151-157 (select_by_mask's mask length)
+                Format,                                        // select.rs:151-157 (select_by_mask's mask length)
+                InvalidValue };                                // series/window.rs:113-116, :567-573, dataframe/window.rs:62-67
     Kind kind;
     Error(Kind k, const std::string &m) : std::runtime_error(m), kind(k) {}
 };
@@ -374,10 +377,84 @@ public:
         return r.second ? std::move(r.first) : OptimizedDataFrame();
     }
 
+    // ---- window statistics (dataframe/window.rs:13-160 over series/window.rs) ----
+    // rolling (:45-79): row i's window [max(0, i+1-w), i+1), or centred start = i >= w/2 ? i - w/2 : 0,
+    // end = min(start+w, n); operation sum / mean / var / std (ddof) / min / max / count, any case; min_periods < 0 =
+    // window_size.  The result: every column, then a Float64Column new_column_name or "{column}_{operation}" (NaN =
+    // None).  Errors before any device call: ColumnNotFound, ColumnTypeMismatch (not Int64 / Float64), InvalidValue
+    // (window_size 0, an unknown operation), DuplicateColumnName.
+    OptimizedDataFrame rolling(size_t window_size, const std::string &column_name, const std::string &operation,
+                               const std::string &new_column_name = "", int64_t min_periods = -1, bool center = false,
+                               int64_t ddof = 1) const {
+        window_column(column_name);
+        if (window_size == 0) throw Error(Error::InvalidValue, "Window size must be greater than 0");
+        pandrs_hip_window_spec sp{PANDRS_HIP_WINDOW_KIND_ROLLING, window_op("rolling", operation, false), (int64_t)window_size,
+                                  min_periods, center ? 1 : 0, 0, ddof, 0.0};
+        return with_window(column_name, operation, new_column_name, sp);
+    }
+    // expanding (:82-119): row i's window [0, i+1), min_periods as given
+    OptimizedDataFrame expanding(size_t min_periods, const std::string &column_name, const std::string &operation,
+                                 const std::string &new_column_name = "", int64_t ddof = 1) const {
+        window_column(column_name);
+        pandrs_hip_window_spec sp{PANDRS_HIP_WINDOW_KIND_EXPANDING, window_op("expanding", operation, false), 0,
+                                  (int64_t)min_periods, 0, 0, ddof, 0.0};
+        return with_window(column_name, operation, new_column_name, sp);
+    }
+    // ewm (:122-160): alpha = 2/(span+1) when span > 0 is given, else alpha (validated to (0, 1], series/window.rs:567-573),
+    // else 1 - exp(-ln2/halflife) (get_alpha, :608); operation mean / std / var (var = the std output squared)
+    OptimizedDataFrame ewm(const std::string &column_name, const std::string &operation, const size_t *span,
+                           const double *alpha, const std::string &new_column_name = "", const double *halflife = nullptr) const {
+        window_column(column_name);
+        double a;
+        if (span) a = 2.0 / ((double)*span + 1.0);
+        else if (alpha) {
+            if (!(*alpha > 0.0 && *alpha <= 1.0)) throw Error(Error::InvalidValue, "Alpha must be between 0 and 1");
+            a = *alpha;
+        } else if (halflife) a = 1.0 - std::exp(-0.69314718055994530942 / *halflife);
+        else throw Error(Error::InvalidValue, "Must specify either span or alpha for EWM");
+        if (!std::isfinite(a)) throw Error(Error::InvalidValue, "EWM alpha is not finite");
+        pandrs_hip_window_spec sp{PANDRS_HIP_WINDOW_KIND_EWM, window_op("EWM", operation, true), 0, 0, 0, 0, 0, a};
+        return with_window(column_name, operation, new_column_name, sp);
+    }
+
 private:
     size_t row_count_ = 0;
     std::shared_ptr<detail::ResidentSet> resident_;
 
+    void window_column(const std::string &name) const {
+        const Column &c = column(name);
+        if (c.index() > 1)
+            throw Error(Error::ColumnTypeMismatch, "Column type mismatch: column '" + name + "' expected Int64 or Float64");
+    }
+    static int32_t window_op(const char *kind, const std::string &operation, bool ewm) {
+        std::string op = operation;
+        std::transform(op.begin(), op.end(), op.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });   // window.rs:54
+        static const std::map<std::string, int32_t> ops = {{"sum", PANDRS_HIP_WINDOW_SUM}, {"mean", PANDRS_HIP_WINDOW_MEAN},
+            {"var", PANDRS_HIP_WINDOW_VAR}, {"std", PANDRS_HIP_WINDOW_STD}, {"min", PANDRS_HIP_WINDOW_MIN},
+            {"max", PANDRS_HIP_WINDOW_MAX}, {"count", PANDRS_HIP_WINDOW_COUNT}};
+        auto it = ops.find(op);
+        if (it == ops.end() || (ewm && it->second != PANDRS_HIP_WINDOW_MEAN && it->second != PANDRS_HIP_WINDOW_STD &&
+                                it->second != PANDRS_HIP_WINDOW_VAR))
+            throw Error(Error::InvalidValue, std::string("Unsupported ") + kind + " operation: " + operation);
+        return it->second;
+    }
+    OptimizedDataFrame with_window(const std::string &column_name, const std::string &operation, const std::string &new_column_name,
+                                   const pandrs_hip_window_spec &sp) const {
+        const std::string name = new_column_name.empty() ? column_name + "_" + operation : new_column_name;   // window.rs:72
+        if (std::find(column_names.begin(), column_names.end(), name) != column_names.end())
+            throw Error(Error::DuplicateColumnName, "Duplicate column name: " + name);
+        Float64Column out;
+        out.data.resize(row_count_);
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_window(detail::context(), mem_space(), &v, (int64_t)row_count_, &sp, PANDRS_HIP_MEM_HOST,
+                                            out.data.data()));
+        }
+        OptimizedDataFrame result;
+        for (size_t c = 0; c < columns.size(); c++) result.add_column(column_names[c], columns[c]);
+        result.add_column(name, std::move(out));
+        return result;
+    }
     pandrs_hip_column condition(const std::string &name) const {
         const Column &c = column(name);
         if (c.index() != 3)

@@ -20,6 +20,8 @@ I64, F64, U32CODE, BOOLBITS, CELL64 = 0, 1, 2, 3, 4
 SUM, MEAN, MIN, MAX, COUNT, STD, VAR, MEDIAN, FIRST, LAST, CUSTOM, NUNIQUE = range(12)
 INNER, LEFT, RIGHT, OUTER = range(4)
 MEM_HOST, MEM_DEVICE = 0, 1
+WINDOW_KIND_ROLLING, WINDOW_KIND_EXPANDING, WINDOW_KIND_EWM = range(3)
+WINDOW_SUM, WINDOW_MEAN, WINDOW_VAR, WINDOW_STD, WINDOW_MIN, WINDOW_MAX, WINDOW_COUNT = range(7)
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -50,6 +52,11 @@ class Timings(C.Structure):
                 ("algorithmic_bytes", C.c_int64), ("n_partitions", C.c_int64),
                 ("table_slots", C.c_int64), ("retries", C.c_int64), ("estimated_groups", C.c_int64),
                 ("absorbed_rows", C.c_int64)]
+
+
+class WindowSpec(C.Structure):             # pandrs_hip_window_spec
+    _fields_ = [("kind", C.c_int32), ("op", C.c_int32), ("window", C.c_int64), ("min_periods", C.c_int64),
+                ("center", C.c_int32), ("reserved", C.c_int32), ("ddof", C.c_int64), ("alpha", C.c_double)]
 
 
 # pandrs_hip_transport: the exchange's collectives as host callbacks (pandrs_hip_comm_adopt_transport)
@@ -133,6 +140,7 @@ SYMBOLS = {
                                             C.c_int64, C.c_int32, _P]),
     "pandrs_hip_filter_indices": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     "pandrs_hip_filter_gather": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_uint64, C.c_int32, _P]),
+    "pandrs_hip_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(WindowSpec), C.c_int32, _P]),
 }
 
 _lib = None

@@ -98,7 +98,7 @@ int32_t pandrs_hip_ctx_destroy(pandrs_hip_ctx *c) try {
     if (!c) return PANDRS_HIP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release();
+    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release();
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) { (void)hipEventDestroy(c->ev_begin[i]); (void)hipEventDestroy(c->ev_end[i]); }
     (void)hipEventDestroy(c->ev_call_begin); (void)hipEventDestroy(c->ev_call_end);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -465,6 +465,13 @@ int32_t pandrs_hip_filter_gather(pandrs_hip_ctx *ctx, int32_t src_mem_space, con
     ST_TRY(pandrs::below_threshold(n_src));
     return pandrs::filter_gather_entry(ctx, src_mem_space, src, n_src, fill_bits, out_mem_space, out);
 } catch (...) { return pandrs::on_exception("pandrs_hip_filter_gather"); }
+
+int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                          const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "window: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::window_entry(ctx, mem_space, col, n_rows, spec, out_mem_space, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_window"); }
 
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {

@@ -246,6 +246,7 @@ struct pandrs_hip_ctx {
     // pairs: fused-join pairs; groups: retained group index (CSR); shuf: retained shuffle buckets)
     pandrs::Arena work, result, staging, temp, result2, result3, side, super, packed, pairs, groups, shuf, absorb, overflow;
     pandrs::Arena filt;          // the retained filter selection (filter.hip)
+    pandrs::Arena win;           // window workspace: van Herk prefix / suffix rows, tile and thread scan states (window.hip)
     pandrs::Options opt;
     pandrs_hip_timings timings{};
     pandrs::GroupbyResult gb, gb2, gb3;   // gb2 / gb3: nested results (slice merges, two-level sub-runs)
@@ -371,6 +372,8 @@ int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
 int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src, uint64_t fill_bits,
                             int32_t out_mem_space, void *out);
 size_t filter_workspace_bytes(int64_t n_rows);
+int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                     const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

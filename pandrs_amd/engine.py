@@ -742,3 +742,29 @@ class Context:
         if st:
             _raise(st)
         return out
+
+    # -- window statistics (rolling / expanding / EWM) ----------------------------------------------------------
+    def window(self, col, n_rows, kind, op, window=0, min_periods=-1, center=False, ddof=1, alpha=0.0, out_device=None):
+        """One window statistic of one I64 / F64 column on the device (pandrs_hip_window; DataFrameWindowExt,
+        src/dataframe/window.rs:13-160 over src/series/window.rs).  `col` is a (data, mask, dtype) triple on the host
+        or the device, or a ResidentColumn; kind / op are L.WINDOW_KIND_* / L.WINDOW_*; window, min_periods (< 0 =
+        window), center and ddof as the rolling spec, alpha resolved by the caller (EWM).  -> n_rows float64 values,
+        NaN for None: a torch tensor on this context's device for device / resident columns (or out_device=True),
+        else a numpy array."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n = int(n_rows)
+        spec = L.WindowSpec(kind=int(kind), op=int(op), window=int(window), min_periods=int(min_periods),
+                            center=1 if center else 0, reserved=0, ddof=int(ddof), alpha=float(alpha))
+        if out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
+        else:
+            out = np.empty(n, np.float64)
+        st = self.lib.pandrs_hip_window(self.h, sp, cc, n, C.byref(spec), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                        _ptr(out) if n else None)
+        if st:
+            _raise(st)
+        return out[:n] if out_device else out

@@ -14,6 +14,7 @@ error behaviour — so the parity tests read like the reference's own tests.
   filter_rows         src/optimized/split_dataframe/row_ops.rs:26-130     OptimizedDataFrame.filter_rows
   par_filter          src/optimized/split_dataframe/parallel.rs:21-230    OptimizedDataFrame.par_filter
   select_by_mask      src/optimized/split_dataframe/select.rs:150-167     OptimizedDataFrame.select_by_mask
+  rolling / expanding / ewm  src/dataframe/window.rs:13-160 over src/series/window.rs  OptimizedDataFrame.rolling / ...
   LazyFrame           src/optimized/lazy.rs:98-170, :186-425          LazyFrame
   AggregateOp         src/optimized/split_dataframe/group/types.rs:11-34   AggregateOp
   JoinType            src/optimized/split_dataframe/join.rs:11-20     JoinType
@@ -22,6 +23,7 @@ This is what the Rust call-outs of INTEGRATION.md §3 do: adapt columns to the C
 device engine, stringify group keys, name result columns.  All arithmetic happens in
 libpandrs_hip.so; there is no CPU implementation of groupby or join here.
 """
+import math
 from decimal import Decimal
 from enum import IntEnum
 
@@ -68,6 +70,10 @@ class InconsistentArrayLengths(ValueError):   # Error::InconsistentArrayLengths 
 
 
 class FormatError(ValueError):        # Error::Format (select.rs:151-157: a mask whose length is not the row count)
+    pass
+
+
+class InvalidValue(ValueError):       # Error::InvalidValue (series/window.rs:113-116, :567-573, dataframe/window.rs:62-67)
     pass
 
 
@@ -308,6 +314,12 @@ def get_context():
     return _default_ctx
 
 
+_WINDOW_OPS = {"sum": L.WINDOW_SUM, "mean": L.WINDOW_MEAN, "var": L.WINDOW_VAR, "std": L.WINDOW_STD, "min": L.WINDOW_MIN,
+               "max": L.WINDOW_MAX, "count": L.WINDOW_COUNT}
+_ROLLING_OPS = set(_WINDOW_OPS.values())
+_EWM_OPS = {L.WINDOW_MEAN, L.WINDOW_STD, L.WINDOW_VAR}
+
+
 # ---------------------------------------------------------------------------------------------- frame
 class OptimizedDataFrame:
     def __init__(self):
@@ -490,6 +502,89 @@ class OptimizedDataFrame:
         for name in self.column_names:
             result.add_column(name, _empty_like(self.column(name)))
         return result
+
+    # -- window statistics (dataframe/window.rs:13-160 over series/window.rs) -------------------------------------
+    def _window_column(self, column_name):
+        if column_name not in self.column_indices:
+            raise ColumnNotFound(column_name)
+        col = self.column(column_name)
+        if col.dtype not in (L.I64, L.F64):
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column type mismatch: column '%s' expected Int64 or Float64, found %s"
+                                     % (column_name, col.column_type()))
+        return col
+
+    @staticmethod
+    def _window_op(kind_name, operation, allowed):
+        op = _WINDOW_OPS.get(str(operation).lower())                    # window.rs:54: to_lowercase
+        if op is None or op not in allowed:
+            raise InvalidValue("Unsupported %s operation: %s" % (kind_name, operation))
+        return op
+
+    def _with_window(self, col, column_name, operation, new_column_name, kind, op, **spec):
+        """A new frame: every column of this one, then a Float64Column named new_column_name or "{column}_{operation}"
+        (window.rs:72), n rows, no null mask (NaN marks a None)."""
+        name = new_column_name if new_column_name is not None else "%s_%s" % (column_name, operation)
+        if name in self.column_indices:
+            raise DuplicateColumnName(name)
+        n = self._row_count
+        values = get_context().window(col.view(), n, kind, op, out_device=False, **spec) if n else np.empty(0)
+        result = OptimizedDataFrame()
+        for c in self.column_names:
+            result.add_column(c, self.column(c))
+        result.add_column(name, Float64Column(values))
+        return result
+
+    def rolling(self, window_size, column_name, operation, new_column_name=None, *, min_periods=None, center=False, ddof=1):
+        """DataFrameWindowExt::rolling (dataframe/window.rs:45-79; Rolling, series/window.rs:107-345): row i's window is
+        [max(0, i+1-w), i+1), or with center start = i >= w/2 ? i - w/2 : 0, end = min(start+w, n).  operation: sum,
+        mean, var, std (ddof), min, max, count, any case.  min_periods defaults to window_size.  Errors, all before any
+        device call: ColumnNotFound, ColumnTypeMismatch (not Int64 / Float64), InvalidValue (window_size 0, an unknown
+        operation, median / quantile), DuplicateColumnName."""
+        col = self._window_column(column_name)
+        if int(window_size) <= 0:
+            raise InvalidValue("Window size must be greater than 0")            # series/window.rs:112-117
+        if min_periods is not None and int(min_periods) < 0:
+            raise InvalidValue("min_periods must be >= 0")
+        if int(ddof) < 0:
+            raise InvalidValue("ddof must be >= 0")
+        op = self._window_op("rolling", operation, _ROLLING_OPS)
+        return self._with_window(col, column_name, operation, new_column_name, L.WINDOW_KIND_ROLLING, op, window=int(window_size),
+                                 min_periods=-1 if min_periods is None else int(min_periods), center=bool(center), ddof=int(ddof))
+
+    def expanding(self, min_periods, column_name, operation, new_column_name=None, *, ddof=1):
+        """DataFrameWindowExt::expanding (dataframe/window.rs:82-119; Expanding, series/window.rs:379-500): row i's
+        window is [0, i+1); min_periods as given (0 allowed).  Same operations and errors as rolling."""
+        col = self._window_column(column_name)
+        if int(min_periods) < 0:
+            raise InvalidValue("min_periods must be >= 0")
+        if int(ddof) < 0:
+            raise InvalidValue("ddof must be >= 0")
+        op = self._window_op("expanding", operation, _ROLLING_OPS)
+        return self._with_window(col, column_name, operation, new_column_name, L.WINDOW_KIND_EXPANDING, op,
+                                 min_periods=int(min_periods), ddof=int(ddof))
+
+    def ewm(self, column_name, operation, span=None, alpha=None, new_column_name=None, *, halflife=None):
+        """DataFrameWindowExt::ewm (dataframe/window.rs:122-160; EWM, series/window.rs:549-724).  alpha = 2/(span+1)
+        when span is given, else alpha (validated to (0, 1], :567-573), else 1 - exp(-ln2/halflife) (get_alpha, :608);
+        none of them is InvalidValue.  operation: mean, std, var (var = the std output squared, :715-724)."""
+        col = self._window_column(column_name)
+        if span is not None:
+            if int(span) < 0:
+                raise InvalidValue("span must be >= 0")
+            a = 2.0 / (float(int(span)) + 1.0)
+        elif alpha is not None:
+            a = float(alpha)
+            if not (0.0 < a <= 1.0):
+                raise InvalidValue("Alpha must be between 0 and 1")
+        elif halflife is not None:
+            with np.errstate(divide="ignore", over="ignore"):
+                a = float(1.0 - np.exp(-math.log(2.0) / np.float64(halflife)))
+        else:
+            raise InvalidValue("Must specify either span or alpha for EWM")
+        if not math.isfinite(a):
+            raise InvalidValue("EWM alpha %r is not finite" % a)
+        op = self._window_op("EWM", operation, _EWM_OPS)
+        return self._with_window(col, column_name, operation, new_column_name, L.WINDOW_KIND_EWM, op, alpha=a)
 
     # -- whole-column reductions (K1: split_dataframe/aggregate.rs:21-215) ----------------------------------
     def _stats(self, name):
