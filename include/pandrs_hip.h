@@ -211,7 +211,10 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
  *   "test_throw"        tests of the exception firewall (ctx may be NULL): 1 = the entry point's host code throws std::bad_alloc
  *                       (-> PANDRS_HIP_ERR_OUT_OF_MEMORY), 2 = std::out_of_range, 3 = a non-std exception, 4 = an oversized
- *                       std::vector::resize (2 - 4 -> PANDRS_HIP_ERR_COMPUTATION, or OUT_OF_MEMORY for bad_alloc); never a crash
+ *                       std::vector::resize (2 - 4 -> PANDRS_HIP_ERR_COMPUTATION, or OUT_OF_MEMORY for bad_alloc); never a crash.
+ *                       5 (needs a ctx) = arms the context once: the next engine run that is nested inside a call (a merge of partial
+ *                       records, a run over spilled rows) throws std::bad_alloc; that call fails with OUT_OF_MEMORY and the context
+ *                       serves the next call as if nothing had happened
  *   "no_census"         1 = the group estimate never takes its second stage (a hash-slice census of a tenth of the rows, run when the
  *                       strided sample shows singletons its repeating keys cannot explain: a long tail behind a broad hot class)
  *   "tail_groups_hint"  tests: the group estimate handed to the tail run of the absorb pass's compact spill (0 = its own sample)

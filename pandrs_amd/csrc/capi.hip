@@ -188,6 +188,11 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
         if (value == 2) { std::vector<int> v; (void)v.at(7); }                 // std::out_of_range, as a container would raise it
         if (value == 3) throw 42;                                              // not a std::exception
         if (value == 4) { std::vector<uint8_t> v; v.resize(~size_t(0) >> 1); } // a real oversized staging resize: std::length_error / bad_alloc
+        if (value == 5) {                                                      // (needs a context) the next NESTED engine run throws: run_engine
+            if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "test_throw = 5 needs a context");
+            std::lock_guard<std::mutex> lock(c->mu);
+            c->test_throw_nested = true;
+        }
         return PANDRS_HIP_OK;
     }
     if (!c || !name) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bad arguments");

@@ -280,6 +280,7 @@ struct pandrs_hip_ctx {
     std::unordered_map<const void *, Resident> resident;
     size_t resident_bytes = 0;
     int quiet = 0;               // > 0: nested engine runs (slice / direct merges) do not record phase events
+    bool test_throw_nested = false;   // set_option("test_throw", 5): the next nested engine run throws std::bad_alloc, once
     int lds_bytes = 0;           // usable LDS per workgroup
     int n_cu = 0;
 };

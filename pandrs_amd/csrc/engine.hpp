@@ -165,6 +165,29 @@ int32_t build_plan(const int32_t *val_dtypes, const uint8_t *val_has_nulls, int 
                    const pandrs_hip_agg_spec *aggs, int n_aggs, Plan &pl);
 int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge, bool partials,
                    int n_aggs, int key_dtype, int n_keys_out = 1, int res_slot = 0);
+// A nested engine run (a merge of partial records, a run over spilled or unplaced rows, a two-level sub-run): it records no phase
+// events and stays off the small / absorb / clustered / two-level paths (c->quiet), and the caller's options, timings and
+// reserve_groups come back when the scope ends: on the normal way out, on an early return (HIP_TRY, ST_TRY) and on unwinding.
+// The site sets the options its run needs in plain assignments after constructing the guard; timings fields the site itself
+// reports are written after the scope has closed.  Outputs of the run are NOT restored: c->capacity_exceeded, c->gb2 / c->gb3,
+// the estimate's findings (clustered_rows, clumped_rows, est_*).
+struct NestedRun {
+    explicit NestedRun(pandrs_hip_ctx *ctx) : c(ctx), opt(ctx->opt), timings(ctx->timings), reserve_groups(ctx->reserve_groups) { c->quiet++; }
+    ~NestedRun() { c->opt = opt; c->timings = timings; c->reserve_groups = reserve_groups; c->quiet--; }
+    NestedRun(const NestedRun &) = delete;
+    NestedRun &operator=(const NestedRun &) = delete;
+private:
+    pandrs_hip_ctx *c;
+    Options opt;
+    pandrs_hip_timings timings;
+    int64_t reserve_groups;
+};
+// A nested run that outgrew one radix level (it cannot go two-level itself) makes the PATH that started it decline (`not_taken`: the
+// ordinary path answers), not the call fail; any other failure is the call's.
+inline int32_t nested_status(pandrs_hip_ctx *c, int32_t st, int32_t not_taken) {
+    if (st && c->capacity_exceeded) { c->capacity_exceeded = false; return not_taken; }
+    return st;
+}
 // work-arena bytes a two-pass radix_partition of n_rows rows with n_cols8 8-byte and n_cols1 byte-wide moved columns takes on top of the single pass
 size_t two_pass_workspace_bytes(int64_t n_rows, int n_cols8, int n_cols1);
 size_t engine_workspace_bytes(int64_t n_rows, int n_cols8, int n_cols1);

@@ -275,18 +275,13 @@ static int32_t hashed_dictionary(pandrs_hip_ctx *c, const KeyDesc &key, int dtyp
     ST_TRY(build_plan(&cdt, &chn, 1, &cspec, 1, cpl));
     RowSource krs;
     krs.n_rows = n_rows; krs.key = key;
-    Options saved = c->opt;
-    c->opt.groups_hint = 0; c->opt.partitions = 0;
-    pandrs_hip_timings tsave = c->timings;
-    c->quiet++;
-    int32_t st = run_engine(c, krs, cpl, /*merge=*/false, /*partials=*/false, 1, dtype, 1);
-    c->quiet--;
-    c->opt = saved;
-    c->timings = tsave;
-    if (st) {
-        if (c->capacity_exceeded) { c->capacity_exceeded = false; return -1; }
-        return st;
+    int32_t st;
+    {
+        NestedRun nested(c);
+        c->opt.groups_hint = 0; c->opt.partitions = 0;
+        st = run_engine(c, krs, cpl, /*merge=*/false, /*partials=*/false, 1, dtype, 1);
     }
+    if (st) return nested_status(c, st, -1);
     const int64_t G = c->gb.n_groups;
     if (G <= 0 || G > dict_cap) return -1;
     uint32_t slots = 1024;
@@ -859,8 +854,7 @@ static int32_t ordered_fold_pass(pandrs_hip_ctx *c, const KeyDesc &key, int64_t 
     for (int a = 0; a < n_aggs; a++) any = any || wants_ordered_fold(aggs[a], vals[aggs[a].col].dtype);
     if (!any) return 0;
     PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
-    c->quiet++;
-    struct Unquiet { pandrs_hip_ctx *c; ~Unquiet() { c->quiet--; } } unq{c};
+    NestedRun nested(c);         // (for c->quiet: the engine runs and partitions below record no phases of their own; nothing else it holds changes here)
     SortedGroups sg;
     ST_TRY(build_sorted_groups(c, key, n_rows, &sg));
     if (sg.G != G) return fail(PANDRS_HIP_ERR_COMPUTATION, "deterministic pass found %lld groups, the engine %lld", (long long)sg.G, (long long)G);

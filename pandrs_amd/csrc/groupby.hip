@@ -945,6 +945,30 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
 // and appends its groups as partial records behind the absorbed ones, and one merge finishes.  No host round trip
 // between the absorb pass and the spill aggregate.  ABSORB_NOT_TAKEN: the caller continues with the ordinary path.
 constexpr int32_t ABSORB_NOT_TAKEN = -1001;
+
+// ---- partial records (key cell, key null flag, state columns states[(1 + s) * stride + i]; column 0 = group size) and their merge:
+// the last step of the direct, absorb and clustered paths and of the sliced partitions.
+static RowSource record_source(const uint64_t *keys, const uint8_t *key_null, const uint64_t *states, size_t stride, int64_t n) {
+    RowSource ms;
+    ms.n_rows = n;
+    ms.key = KeyDesc{keys, nullptr, key_null, DT_CELL};
+    ms.merge_states = states;
+    ms.merge_stride = stride;
+    return ms;
+}
+enum : unsigned { MERGE_NO_ABSORB = 1, MERGE_NO_SLICE = 2, MERGE_AUTO_PARTITIONS = 4 };     // what the sites' merges override besides
+// One nested run that merges `ms` into result slot `res_slot`.  The records are few: never the direct path again; `hint` bounds
+// their groups, so no second estimate is taken.
+static int32_t merge_records(pandrs_hip_ctx *c, const RowSource &ms, int64_t hint, unsigned over, const Plan &pl, bool partials,
+                             int n_aggs, int key_dtype, int n_keys_out, int res_slot) {
+    NestedRun nested(c);
+    c->opt.no_direct = 1;
+    if (over & MERGE_NO_ABSORB) c->opt.no_absorb = 1;
+    if (over & MERGE_NO_SLICE) c->opt.no_slice = 1;
+    if (over & MERGE_AUTO_PARTITIONS) c->opt.partitions = 0;
+    c->opt.groups_hint = std::max<int64_t>(hint, 1);
+    return run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, n_keys_out, res_slot);
+}
 static int64_t absorb_table_slots(const pandrs_hip_ctx *c, int lds_states) {
     return ((int64_t)(((size_t)c->lds_bytes - 512 - 640) / (12 + 8 * (size_t)lds_states)) - 2) & ~int64_t(3);
 }
@@ -1080,13 +1104,11 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
             // an oversized partition, the overflow run of an underestimated tail), so slot res_slot + 1 must not hold anything yet.
             // The absorbed records live in c->temp, which no run below touches (no_direct, no_absorb).
             // (Merging the spilled rows' groups as partial records with the absorbed ones cost 11 ms for a 16 M-group tail.)
-            Options saved = c->opt;
-            pandrs_hip_timings tsave = c->timings;
-            c->opt.no_direct = 1; c->opt.no_absorb = 1; c->opt.partitions = 0;
-            c->quiet++;
             const int64_t hot_bound = std::min<int64_t>((int64_t)T + 2, n_abs);     // image keys + the NULL key + the sentinel-valued key
             int32_t st2;
             {
+                NestedRun nested(c);
+                c->opt.no_direct = 1; c->opt.no_absorb = 1; c->opt.partitions = 0;
                 RowSource sp;
                 sp.n_rows = n_compact;
                 sp.key = KeyDesc{ck, nullptr, nullptr, DT_CELL};          // (NULL keys and the sentinel-valued key are always absorbed)
@@ -1096,37 +1118,23 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
                     sp.val_valid_bytes[s2] = has_v ? cvalid[s2] : nullptr;
                 }
                 c->opt.groups_hint = std::max<int64_t>(c->opt.tail_groups_hint, 0);   // (0:) its own estimate: the tail's cardinality is what the first one could not see
-                c->reserve_groups = hot_bound;
+                c->reserve_groups = hot_bound;           // (for this run only: the guard takes it back before the merge below)
                 st2 = run_engine(c, sp, pl, /*merge=*/false, partials, n_aggs, key_dtype, n_keys_out, res_slot);
-                c->reserve_groups = 0;
             }
             GroupbyResult &r2 = c->gb2;
             int64_t n_hot = 0;
             if (!st2 && n_abs > 0) {
-                RowSource ms;
-                ms.n_rows = n_abs;
-                ms.key = KeyDesc{rk, nullptr, rn, DT_CELL};
-                ms.merge_states = rst;
-                ms.merge_stride = dcap;
-                c->opt.groups_hint = std::max<int64_t>(hot_bound, 1);
-                st2 = run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, 1, res_slot + 1);
+                st2 = merge_records(c, record_source(rk, rn, rst, dcap, n_abs), hot_bound, MERGE_NO_ABSORB | MERGE_AUTO_PARTITIONS, pl,
+                                    partials, n_aggs, key_dtype, 1, res_slot + 1);
                 if (!st2) n_hot = r2.n_groups;
             }
-            c->quiet--;
-            c->opt = saved;
-            pandrs_hip_timings tnested = c->timings;
-            c->timings = tsave;
-            if (st2) {
-                // the tail alone holds more groups than one radix level takes (a nested run cannot go two-level): the ordinary path answers
-                if (c->capacity_exceeded) { c->capacity_exceeded = false; return ABSORB_NOT_TAKEN; }
-                return st2;
-            }
+            // the tail alone holds more groups than one radix level takes (a nested run cannot go two-level): the ordinary path answers
+            if (st2) return nested_status(c, st2, ABSORB_NOT_TAKEN);
             GroupbyResult &res = c->gb;
             if (n_hot > 0) {
                 ST_TRY(append_groups(c, res, (size_t)res.cap, r2, partials, pl, n_aggs));
                 HIP_TRY(hipStreamSynchronize(c->stream));
             }
-            (void)tnested;
             c->timings.estimated_groups = est;
             c->timings.absorbed_rows = N - n_compact;
             c->timings.n_partitions = -1;
@@ -1150,20 +1158,9 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
     uint32_t *hs = reinterpret_cast<uint32_t *>(c->pinned) + 1100;                           // own corner: the merge below reads its counters at +0
     HIP_TRY(hipMemcpyAsync(hs, counters + (compact ? 4 : 3), 4, hipMemcpyDeviceToHost, c->stream));   // rows spilled: reported, not needed to continue
     // one merge of everything (the direct path's last step)
-    RowSource ms;
-    ms.n_rows = h4[2];
-    ms.key = KeyDesc{rk, nullptr, rn, DT_CELL};
-    ms.merge_states = rst;
-    ms.merge_stride = dcap;
-    Options saved = c->opt;
-    c->opt.no_direct = 1; c->opt.no_absorb = 1;
-    c->opt.groups_hint = std::max<int64_t>(std::min<int64_t>(est, ms.n_rows), 1);
-    pandrs_hip_timings tsave = c->timings;
-    c->quiet++;
-    const int32_t st = run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, n_keys_out, res_slot);
-    c->quiet--;
-    c->opt = saved;
-    c->timings = tsave;
+    const int64_t n_rec = h4[2];
+    const int32_t st = merge_records(c, record_source(rk, rn, rst, dcap, n_rec), std::min<int64_t>(est, n_rec), MERGE_NO_ABSORB, pl,
+                                     partials, n_aggs, key_dtype, n_keys_out, res_slot);
     c->timings.estimated_groups = est;
     c->timings.absorbed_rows = N - (int64_t)hs[0];         // (the merge synchronised the stream)
     c->timings.n_partitions = hs[0] ? (compact ? -1 : PS) : 0;   // nothing spilled: no radix partition took part (the few-groups case); -1: compact spill
@@ -1171,8 +1168,7 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
     c->timings.retries = 0;
     // (the merge is a nested run: it cannot go two-level.  More groups among the records than one radix level takes — only with a
     // tiny test level, p_max — hands the call back to the ordinary path instead of failing it)
-    if (st && c->capacity_exceeded) { c->capacity_exceeded = false; return ABSORB_NOT_TAKEN; }
-    return st;
+    return nested_status(c, st, ABSORB_NOT_TAKEN);
 }
 
 // ---- rows clustered by key (sorted input, input grouped by key, time-ordered keys) ------------------------------------------------
@@ -1275,31 +1271,19 @@ static int32_t run_clustered(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     const uint32_t failed = hp[1], n_rec = hp[2];
     if (failed) return CLUSTERED_NOT_TAKEN;          // a chunk held more runs than its table takes, or the record buffer ran out
-    RowSource ms;
-    ms.n_rows = n_rec;
-    ms.key = KeyDesc{rk, nullptr, rn, DT_CELL};
-    ms.merge_states = rst;
-    ms.merge_stride = dcap;
-    Options saved = c->opt;
-    c->opt.no_direct = 1; c->opt.no_absorb = 1;
-    c->opt.groups_hint = std::max<int64_t>(std::min<int64_t>(est, ms.n_rows), 1);
-    pandrs_hip_timings tsave = c->timings;
-    c->quiet++;
-    const int32_t st = run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, n_keys_out, res_slot);
-    c->quiet--;
-    c->opt = saved;
-    c->timings = tsave;
+    const int32_t st = merge_records(c, record_source(rk, rn, rst, dcap, n_rec), std::min<int64_t>(est, n_rec), MERGE_NO_ABSORB, pl,
+                                     partials, n_aggs, key_dtype, n_keys_out, res_slot);
     c->timings.estimated_groups = est;
     c->timings.n_partitions = -2;                    // (reported: no radix partition of the rows; -2 = the clustered-rows pass)
     c->timings.table_slots = T;
     c->timings.retries = 0;
-    if (st && c->capacity_exceeded) { c->capacity_exceeded = false; return CLUSTERED_NOT_TAKEN; }
-    return st;
+    return nested_status(c, st, CLUSTERED_NOT_TAKEN);
 }
 
 int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge,
                           bool partials, int n_aggs, int key_dtype, int n_keys_out, int res_slot) {
     if (res_slot < 0 || res_slot > 2) return fail(PANDRS_HIP_ERR_COMPUTATION, "engine nesting too deep");
+    if (c->test_throw_nested && c->quiet > 0) { c->test_throw_nested = false; throw std::bad_alloc(); }     // tests: what a host allocation below could do
     GroupbyResult &res = res_slot == 0 ? c->gb : (res_slot == 1 ? c->gb2 : c->gb3);
     Arena &rarena = res_slot == 0 ? c->result : (res_slot == 1 ? c->result2 : c->result3);
     res = GroupbyResult{};
@@ -1496,20 +1480,9 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
             HIP_TRY(hipStreamSynchronize(c->stream));
             if (h[1] == 0) {
                 c->timings.n_partitions = 0; c->timings.table_slots = Td;
-                RowSource ms;
-                ms.n_rows = h[0];
-                ms.key = KeyDesc{rk, nullptr, rn, DT_CELL};
-                ms.merge_states = rst;
-                ms.merge_stride = dcap;
-                Options saved = c->opt;
-                c->opt.no_direct = 1;                 // the merge input is tiny; never recurse
-                c->opt.groups_hint = std::max<int64_t>(est, 1);   // cardinality is known: no second estimate
-                pandrs_hip_timings tsave = c->timings;
-                c->quiet++;
-                int32_t st = run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, n_keys_out, res_slot);
-                c->quiet--;
-                c->opt = saved;
-                c->timings = tsave;
+                // (the merge input is tiny and its cardinality is known)
+                const int32_t st = merge_records(c, record_source(rk, rn, rst, dcap, h[0]), est, 0, pl, partials, n_aggs, key_dtype,
+                                                 n_keys_out, res_slot);
                 c->timings.estimated_groups = est;
                 return st;
             }
@@ -1933,25 +1906,13 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
             const int64_t n_ov = ov_cap ? (int64_t)h[6] : 0;       // (read NOW: the nested runs below reuse the pinned words)
             if (n_side > 0) {
                 // merge the partial records of the sliced partitions and append their groups
-                RowSource ms;
-                ms.n_rows = n_side;
-                ms.key = KeyDesc{aa.side_keys, nullptr, aa.side_null, DT_CELL};
-                ms.merge_states = aa.side_states;
-                ms.merge_stride = side_cap;
+                RowSource ms = record_source(aa.side_keys, aa.side_null, aa.side_states, side_cap, n_side);
                 for (int s2 = 0; s2 < pl.n_src; s2++) {        // First / Last finish with a look-up in the original column
                     ms.fin_data[s2] = rs.fin_data[s2] ? rs.fin_data[s2] : rs.val_data[s2];
                     ms.fin_null_bits[s2] = rs.fin_data[s2] ? rs.fin_null_bits[s2] : rs.val_null_bits[s2];
                 }
-                Options saved = c->opt;
-                c->opt.no_slice = 1; c->opt.no_direct = 1; c->opt.partitions = 0;
-                c->opt.groups_hint = std::max<int64_t>(std::min<int64_t>(n_side, est), 1);   // an upper bound: no second estimate
-                pandrs_hip_timings tsave = c->timings;
-                c->quiet++;
-                int32_t st = run_engine(c, ms, pl, /*merge=*/true, partials, n_aggs, key_dtype, 1, res_slot + 1);
-                c->quiet--;
-                c->opt = saved;
-                c->timings = tsave;
-                if (st) return st;
+                ST_TRY(merge_records(c, ms, std::min<int64_t>(n_side, est), MERGE_NO_SLICE | MERGE_AUTO_PARTITIONS, pl, partials, n_aggs,
+                                     key_dtype, 1, res_slot + 1));
                 GroupbyResult &r2 = res_slot == 0 ? c->gb2 : c->gb3;
                 ST_TRY(append_groups(c, res, cap, r2, partials, pl, n_aggs));
                 HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1966,15 +1927,13 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
                     os.val_null_bits[s2] = nullptr;
                     os.val_valid_bytes[s2] = (uni_profile & 1) ? aa.ov_valid[s2] : nullptr;
                 }
-                Options saved = c->opt;
-                c->opt.partitions = 0; c->opt.no_absorb = 1;
-                c->opt.groups_hint = n_ov <= 4096 ? n_ov : 0;       // (a handful of rows: every row its own group at worst — no sample, no round trip for it)
-                pandrs_hip_timings tsave = c->timings;
-                c->quiet++;
-                int32_t st = run_engine(c, os, pl, /*merge=*/false, partials, n_aggs, key_dtype, 1, res_slot + 1);
-                c->quiet--;
-                c->opt = saved;
-                c->timings = tsave;
+                int32_t st;
+                {
+                    NestedRun nested(c);
+                    c->opt.partitions = 0; c->opt.no_absorb = 1;
+                    c->opt.groups_hint = n_ov <= 4096 ? n_ov : 0;       // (a handful of rows: every row its own group at worst — no sample, no round trip for it)
+                    st = run_engine(c, os, pl, /*merge=*/false, partials, n_aggs, key_dtype, 1, res_slot + 1);
+                }
                 // the nested run cannot leave one radix level (it is not the call's own run): when the unplaced rows alone hold more
                 // groups than one level takes, THIS attempt has failed — more partitions, or the two-level path, below — and the call
                 // must not fail with the nested run's error (fuzz, round 4: p_max = 24 with 900 K groups)
@@ -2087,37 +2046,35 @@ static int32_t run_two_level(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     else res.aggs = rarena.take<double>(cap * out_cols + 32);
     if (!res.keys || !res.key_null || (!res.states && !res.aggs)) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "result arena too small");
 
-    Options saved = c->opt;
-    pandrs_hip_timings tsave = c->timings;
-    c->opt.no_direct = 1; c->opt.groups_hint = 0; c->opt.partitions = 0;
     int32_t st = 0;
     c->capacity_exceeded = false;
-    for (int64_t sp = 0; sp <= K && !st; sp++) {          // sp == K: the NULL-key rows
-        const uint32_t b = off[sp], e2 = off[sp + 1];
-        if (b == e2) continue;
-        RowSource sub;
-        sub.n_rows = (int64_t)e2 - b;
-        sub.key = KeyDesc{spk + b, nullptr, sp == K ? ones : nullptr, DT_CELL};
-        for (int s2 = 0; s2 < n_src; s2++) {
-            sub.val_data[s2] = spv[s2] + b;
-            sub.val_valid_bytes[s2] = spvalid[s2] ? spvalid[s2] + b : nullptr;
-            sub.fin_data[s2] = rs.fin_data[s2] ? rs.fin_data[s2] : rs.val_data[s2];
-            sub.fin_null_bits[s2] = rs.fin_data[s2] ? rs.fin_null_bits[s2] : rs.val_null_bits[s2];
+    {
+        // one guard around all sub-runs: what runs between them (append_groups, a synchronise) reads nothing of what it holds
+        NestedRun nested(c);
+        c->opt.no_direct = 1; c->opt.groups_hint = 0; c->opt.partitions = 0;
+        for (int64_t sp = 0; sp <= K && !st; sp++) {          // sp == K: the NULL-key rows
+            const uint32_t b = off[sp], e2 = off[sp + 1];
+            if (b == e2) continue;
+            RowSource sub;
+            sub.n_rows = (int64_t)e2 - b;
+            sub.key = KeyDesc{spk + b, nullptr, sp == K ? ones : nullptr, DT_CELL};
+            for (int s2 = 0; s2 < n_src; s2++) {
+                sub.val_data[s2] = spv[s2] + b;
+                sub.val_valid_bytes[s2] = spvalid[s2] ? spvalid[s2] + b : nullptr;
+                sub.fin_data[s2] = rs.fin_data[s2] ? rs.fin_data[s2] : rs.val_data[s2];
+                sub.fin_null_bits[s2] = rs.fin_data[s2] ? rs.fin_null_bits[s2] : rs.val_null_bits[s2];
+            }
+            sub.row_index = sprow ? sprow + b : nullptr;
+            if (merge) {
+                sub.merge_gsize = spg + b;
+                for (int k = 0; k < n_mcols; k++) sub.merge_cols[k] = spm[k] + b;
+                sub.merge_states = spm[0];          // non-null marker only; merge_cols carry the data
+            }
+            st = run_engine(c, sub, pl, merge, partials, n_aggs, key_dtype, 1, res_slot + 1);
+            if (!st) st = append_groups(c, res, cap, c->gb2, partials, pl, n_aggs);
+            if (!st) HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        sub.row_index = sprow ? sprow + b : nullptr;
-        if (merge) {
-            sub.merge_gsize = spg + b;
-            for (int k = 0; k < n_mcols; k++) sub.merge_cols[k] = spm[k] + b;
-            sub.merge_states = spm[0];          // non-null marker only; merge_cols carry the data
-        }
-        c->quiet++;
-        st = run_engine(c, sub, pl, merge, partials, n_aggs, key_dtype, 1, res_slot + 1);
-        c->quiet--;
-        if (!st) st = append_groups(c, res, cap, c->gb2, partials, pl, n_aggs);
-        if (!st) HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->opt = saved;
-    c->timings = tsave;
     c->timings.n_partitions = K; c->timings.retries = 0; c->timings.estimated_groups = est;
     if (st && c->capacity_exceeded && K < P_MAX) { c->capacity_exceeded = false; continue; }
     if (st) return st;

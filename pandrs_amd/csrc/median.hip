@@ -893,8 +893,7 @@ int32_t median_pass(pandrs_hip_ctx *c, const KeyDesc &key, int64_t n_rows, const
     if (n_rows >= (int64_t(1) << 32) - 16384)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "median: more than 2^32 rows per call");
     PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
-    c->quiet++;
-    struct Unquiet { pandrs_hip_ctx *c; ~Unquiet() { c->quiet--; } } unq{c};
+    NestedRun nested(c);         // (for c->quiet: the engine runs and partitions below record no phases of their own; nothing else it holds changes here)
     uint32_t cap_tab = 64;
     while ((double)cap_tab < 1.5 * (double)G) cap_tab <<= 1;
     const size_t ws = engine_workspace_bytes(n_rows, 4, 1) + two_pass_workspace_bytes(n_rows, 1, 1) + segsort_workspace_bytes(n_rows, P_MAX + 2, 8)

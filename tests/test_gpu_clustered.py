@@ -12,6 +12,7 @@ from tests.helpers import assert_groupby_equal
 pytestmark = pytest.mark.gpu
 
 CLUSTERED = -2          # timings()["n_partitions"] of a call the clustered-rows pass answered
+COMPACT_SPILL = -1      # ... of a call the absorb pass answered with a compact spill
 
 
 @pytest.fixture(scope="module")
@@ -173,6 +174,61 @@ def test_a_chunk_with_more_runs_than_its_table_hands_the_call_back(ctx):
         run_and_check(ctx, [(k, None, O.I64)], n, vals, aggs, [O.I64], exact=[1, 2, 3], expect_clustered=False)
     finally:
         ctx.set_option("no_clustered", 0)
+
+
+@pytest.mark.parametrize("site", ["clustered_merge", "compact_spill_tail"])
+def test_the_context_survives_a_throw_inside_a_nested_run(site):
+    """Engine runs nested inside a call run with options of their own, with `quiet` raised (no phase events, no small / absorb /
+    clustered path) and sometimes with `reserve_groups` set.  A host exception inside one (std::bad_alloc from its vectors; here
+    set_option("test_throw", 5), which makes the next nested run throw at its entry) fails that call with OUT_OF_MEMORY, and
+    everything the nested run was given must be taken back while the exception unwinds: the same call on the same context then takes
+    the same path as before, reports the same figures, records phase events again and gives the oracle's answer.
+    Sites: the merge of the clustered pass's chunk records (sorted keys), and the run over the spilled rows of the absorb pass's
+    compact spill (a hot set in front of a long tail: test_gpu_groupby.py
+    test_compact_spill_with_nested_runs_and_composite_keys), where no_absorb and reserve_groups would stick as well."""
+    import pandrs_amd as pa
+    from pandrs_amd import _lib as L
+    if site == "clustered_merge":
+        rng = np.random.default_rng(11)
+        n, g = 3_000_001, 40_000
+        keys = [(mixed(np.sort(rng.integers(0, g, n))), None, O.I64)]
+        vals = [(rng.normal(100, 10, n), None, O.F64) for _ in range(4)]
+        aggs = [(c, op) for c in range(4) for op in (O.SUM, O.MEAN, O.MIN, O.MAX)] + [(0, O.COUNT)]
+        exact, path = [2, 3, 6, 7, 10, 11, 14, 15, 16], CLUSTERED
+    else:
+        rng = np.random.default_rng(11)
+        n, g = 17_000_000, 2_000_000
+        hot = rng.random(n) < 0.85                   # 85 % of the rows on 800 keys, the rest on 2 M
+        k = mixed(np.where(hot, rng.integers(0, 800, n), rng.integers(0, g, n)))
+        k[::100_003] = -1
+        keys = [(k, O.pack_mask(rng.random(n) < 0.001), O.I64)]
+        v = rng.standard_normal(n)
+        v[::50_021] = np.nan
+        vals = [(v, O.pack_mask(rng.random(n) < 0.02), O.F64), (rng.standard_normal(n), O.pack_mask(rng.random(n) < 0.3), O.F64)]
+        aggs = [(0, O.SUM), (0, O.MIN), (0, O.MAX), (0, O.MEAN), (1, O.SUM), (1, O.MIN), (1, O.MAX), (1, O.COUNT)]
+        exact, path = [1, 2, 5, 6, 7], COMPACT_SPILL
+    want = O.groupby_agg(keys, n, vals, aggs)
+    c = pa.Context(0)
+    try:
+        c.set_option("no_small", 1)
+        c.groupby_agg(keys, n, vals, aggs)
+        t1 = c.timings()
+        print("first call:", t1)
+        assert t1["n_partitions"] == path, t1        # (the input reaches the site at all)
+        c.set_option("test_throw", 5)
+        with pytest.raises(pa.engine.PandrsHipError) as err:
+            c.groupby_agg(keys, n, vals, aggs)
+        assert err.value.status == L.ERR_OUT_OF_MEMORY, err.value
+        got = c.groupby_agg(keys, n, vals, aggs)
+        t3 = c.timings()
+        print("after the throw:", t3)
+        assert_groupby_equal(got, want, [O.I64], int_exact_rows=exact)
+        assert t3["n_partitions"] == path and t3["retries"] == 0, (t1, t3)
+        assert t3["phase_ms"], t3                     # phase events are recorded again: quiet is back to 0
+        if path == COMPACT_SPILL:
+            assert t3["absorbed_rows"] > 0.5 * n, t3          # (85 % of the rows are on the hot keys)
+    finally:
+        c.close()
 
 
 def test_sorted_config2_at_full_size():
