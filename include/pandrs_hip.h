@@ -16,6 +16,8 @@
  *   - `mem_space` says where the caller's column / output pointers live:
  *     PANDRS_HIP_MEM_HOST (library stages H2D/D2H itself) or PANDRS_HIP_MEM_DEVICE
  *     (pointers are HBM addresses on the context's device; nothing crosses PCIe).
+ *     Any other value of a `mem_space` / `out_mem_space` argument is
+ *     PANDRS_HIP_ERR_INVALID_ARGUMENT at every entry point, before anything is read.
  *     Device inputs must be COMPLETE when a call starts: the context's stream is
  *     non-blocking, so a caller that produced them on another stream synchronises that
  *     stream first.  Device outputs are complete when the call returns.

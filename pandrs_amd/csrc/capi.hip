@@ -293,6 +293,7 @@ int32_t pandrs_hip_groupby_merge(pandrs_hip_ctx *ctx, int32_t mem_space, int32_t
 int32_t pandrs_hip_groupby_fetch(pandrs_hip_ctx *c, int32_t mem_space, uint64_t *const *out_keys,
                                  uint8_t *const *out_key_null, double *const *out_aggs) try {
     if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+    ST_TRY(pandrs::check_mem_space("groupby_fetch", mem_space));
     std::lock_guard<std::mutex> lock(c->mu);
     pandrs::GroupbyResult &r = c->gb;
     if (!r.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no groupby result retained in this context");
@@ -323,6 +324,7 @@ int32_t pandrs_hip_groupby_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const
 int32_t pandrs_hip_groupby_indices_fetch(pandrs_hip_ctx *c, int32_t mem_space, uint64_t *const *out_keys,
                                          uint8_t *const *out_key_null, int64_t *out_offsets, int64_t *out_rows) try {
     if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+    ST_TRY(pandrs::check_mem_space("groupby_indices_fetch", mem_space));
     std::lock_guard<std::mutex> lock(c->mu);
     pandrs::GroupsResult &r = c->gr;
     if (!r.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no group index retained in this context");
@@ -351,6 +353,7 @@ int32_t pandrs_hip_shuffle_split(pandrs_hip_ctx *ctx, int32_t mem_space, const p
 int32_t pandrs_hip_shuffle_fetch(pandrs_hip_ctx *c, int32_t mem_space, uint64_t *out_cells, uint8_t *out_key_null,
                                  uint64_t *const *out_payload, uint8_t *const *out_payload_null) try {
     if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+    ST_TRY(pandrs::check_mem_space("shuffle_fetch", mem_space));
     std::lock_guard<std::mutex> lock(c->mu);
     pandrs::ShuffleResult &r = c->sh;
     if (!r.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no shuffle result retained in this context");
@@ -389,6 +392,7 @@ int32_t pandrs_hip_join_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pa
 int32_t pandrs_hip_join_fetch(pandrs_hip_ctx *c, int32_t mem_space, int64_t *out_left_idx,
                               int64_t *out_right_idx) try {
     if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+    ST_TRY(pandrs::check_mem_space("join_fetch", mem_space));
     std::lock_guard<std::mutex> lock(c->mu);
     if (!c->jn.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no join result retained in this context");
     HIP_TRY(hipSetDevice(c->device));

@@ -388,4 +388,83 @@ inline size_t dtype_bytes(int dtype, int64_t n) {
     }
 }
 
+// ---- memory spaces, and the staging of host buffers through the context's `staging` arena ------
+// The one check of a mem_space / out_mem_space argument: every entry point that takes one calls it before it reads anything.
+inline int32_t check_mem_space(const char *entry, int32_t space, int32_t out_space = PANDRS_HIP_MEM_DEVICE) {
+    for (int32_t s : {space, out_space})
+        if (s != PANDRS_HIP_MEM_HOST && s != PANDRS_HIP_MEM_DEVICE)
+            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "%s: bad memory space %d (PANDRS_HIP_MEM_HOST or PANDRS_HIP_MEM_DEVICE)", entry, s);
+    return 0;
+}
+
+struct ColView { const void *data; const uint8_t *mask; };     // a column as the kernels read it
+
+// One call's staging: the caller sums what it is going to stage (in_size / col_size / out_size, slot() for device scratch
+// of its own) into ONE reserve(), then takes the slots in any order.  A slot is sized by slot() on both sides, so the sum
+// and the takes cannot drift apart.  Buffers of a device-space call pass through untouched and cost nothing.
+struct Stager {
+    pandrs_hip_ctx *c;
+    int32_t space, out_space;
+    int32_t status = 0;                    // sticky: the first failure; in() / out() / scratch() are no-ops after it
+    void *out_host = nullptr, *out_dev = nullptr;
+    std::vector<const void *> pinned;      // host ranges page-locked for this call (GpuConfig.use_pinned_memory)
+
+    Stager(pandrs_hip_ctx *ctx, int32_t in_space, int32_t out_sp = PANDRS_HIP_MEM_DEVICE) : c(ctx), space(in_space), out_space(out_sp) {}
+    Stager(const Stager &) = delete;
+    ~Stager() {
+        if (pinned.empty()) return;
+        (void)hipStreamSynchronize(c->stream);   // the DMA engines may still be reading the ranges
+        for (const void *p : pinned) (void)hipHostUnregister(const_cast<void *>(p));
+    }
+
+    static size_t slot(size_t bytes) { return Arena::padded(bytes + 16); }
+    // (an empty or absent buffer is never dereferenced: nothing to stage)
+    size_t in_size(const void *p, size_t bytes) const { return p && bytes && space == PANDRS_HIP_MEM_HOST ? slot(bytes) : 0; }
+    size_t col_size(const pandrs_hip_column &col, int64_t n) const {
+        return in_size(col.data, dtype_bytes(col.dtype, n)) + in_size(col.null_mask, (size_t)(n + 7) / 8);
+    }
+    size_t out_size(const void *p, size_t bytes) const { return p && out_space == PANDRS_HIP_MEM_HOST ? slot(bytes) : 0; }
+    int32_t reserve(size_t total) { return total ? c->staging.ensure(total, c->stream) : 0; }
+
+    void *take(size_t bytes) {
+        if (status) return nullptr;
+        void *d = c->staging.take<uint8_t>(bytes + 16);
+        if (!d) status = fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
+        return d;
+    }
+    template <typename T>
+    T *scratch(size_t count) { return static_cast<T *>(take(count * sizeof(T))); }
+
+    // copies `bytes` from a caller pointer into the staging arena when it lives on the host
+    const void *in(const void *p, size_t bytes) {
+        if (!in_size(p, bytes) || status) return p;
+        void *d = take(bytes);
+        if (!d) return nullptr;
+        if (config_use_pinned_memory() && bytes >= (size_t(1) << 20) &&
+            hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) == hipSuccess)
+            pinned.push_back(p);                // (a range that cannot be registered is simply copied pageable)
+        else
+            (void)hipGetLastError();
+        hipError_t e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) status = fail(PANDRS_HIP_ERR_COMPUTATION, "H2D copy failed: %s", hipGetErrorString(e));
+        return d;
+    }
+    // a column over n rows: data by dtype_bytes, mask by (n + 7) / 8
+    ColView col(const pandrs_hip_column &col, int64_t n) {
+        return ColView{in(col.data, dtype_bytes(col.dtype, n)), static_cast<const uint8_t *>(in(col.null_mask, (size_t)(n + 7) / 8))};
+    }
+    // where the kernels write the call's result: the caller's buffer itself, or a slot that copy_back() copies to it
+    template <typename T>
+    T *out(T *p, size_t bytes) {
+        if (!out_size(p, bytes)) return p;
+        out_host = p;
+        return static_cast<T *>(out_dev = take(bytes));
+    }
+    int32_t copy_back(size_t bytes) {
+        if (status) return status;
+        if (out_dev && bytes) HIP_TRY(hipMemcpyAsync(out_host, out_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+};
+
 }  // namespace pandrs

@@ -529,6 +529,7 @@ int32_t pandrs_hip_dist_groupby_agg(pandrs_hip_ctx *ctx, pandrs_hip_comm *comm, 
                                     const pandrs_hip_agg_spec *aggs, int32_t n_aggs, int64_t *out_n_groups) try {
     if (!ctx || !comm || !keys || !out_n_groups || n_rows < 0 || n_vals < 0 || n_aggs < 0 || (n_vals && !vals) || (n_aggs && !aggs))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "dist_groupby_agg: bad arguments");
+    ST_TRY(pandrs::check_mem_space("dist_groupby_agg", mem_space));
     if (comm->aborted) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "this communicator was aborted after a rank-local failure: create a new one");
     HIP_TRY(hipSetDevice(ctx->device));
     bool mergeable = n_keys == 1;

@@ -10,33 +10,6 @@
 
 namespace pandrs {
 
-// ---- staging helpers (host mem_space) -----------------------------------------------------------
-struct Stager {
-    pandrs_hip_ctx *c;
-    int32_t space;
-    int32_t status = 0;
-    std::vector<const void *> pinned;      // host ranges page-locked for this call (GpuConfig.use_pinned_memory)
-    // copies `bytes` from a caller pointer into the staging arena when it lives on the host
-    const void *in(const void *p, size_t bytes) {
-        if (!p || space == PANDRS_HIP_MEM_DEVICE || status || bytes == 0) return p;      // (an empty column is never dereferenced: nothing to stage)
-        void *d = c->staging.take<uint8_t>(bytes + 16);
-        if (!d) { status = fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small"); return nullptr; }
-        if (config_use_pinned_memory() && bytes >= (size_t(1) << 20) &&
-            hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) == hipSuccess)
-            pinned.push_back(p);                // (a range that cannot be registered is simply copied pageable)
-        else
-            (void)hipGetLastError();
-        hipError_t e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) status = fail(PANDRS_HIP_ERR_COMPUTATION, "H2D copy failed: %s", hipGetErrorString(e));
-        return d;
-    }
-    ~Stager() {
-        if (pinned.empty()) return;
-        (void)hipStreamSynchronize(c->stream);   // the DMA engines may still be reading the ranges
-        for (const void *p : pinned) (void)hipHostUnregister(const_cast<void *>(p));
-    }
-};
-
 static int32_t check_cols(const pandrs_hip_column *cols, int n, const char *what, bool keys = false) {
     for (int i = 0; i < n; i++) {
         if (cols[i].dtype < PANDRS_HIP_I64 || cols[i].dtype > (keys ? PANDRS_HIP_CELL64 : PANDRS_HIP_BOOLBITS))
@@ -308,10 +281,10 @@ static int32_t pack_multi_key(pandrs_hip_ctx *c, Stager &stg, const pandrs_hip_c
     // composite key: per-column code widths from a min/max pass, then one packed cell per row
     PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
     pd.n_keys = n_keys;
-    for (int k = 0; k < n_keys; k++)
-        pd.key[k] = KeyDesc{k == 0 ? key.data : stg.in(keys[k].data, dtype_bytes(keys[k].dtype, n_rows)),
-                            k == 0 ? key.null_bits : (const uint8_t *)stg.in(keys[k].null_mask, (n_rows + 7) / 8),
-                            nullptr, keys[k].dtype};
+    for (int k = 0; k < n_keys; k++) {
+        const ColView v = k == 0 ? ColView{key.data, key.null_bits} : stg.col(keys[k], n_rows);
+        pd.key[k] = KeyDesc{v.data, v.mask, nullptr, keys[k].dtype};
+    }
     if (stg.status) return stg.status;
     ST_TRY(c->work.ensure(1 << 16, c->stream));
     uint64_t *mm = c->work.take<uint64_t>(2 * MAX_KEYS);
@@ -399,6 +372,7 @@ int32_t groupby_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_col
     if (!c || !out_n_groups || n_rows < 0 || n_keys < 1 || n_vals < 0 || n_aggs < 0 || !keys ||
         (n_vals && !vals) || (n_aggs && !aggs))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "groupby: bad arguments");
+    ST_TRY(check_mem_space("groupby", mem_space));
     if (n_keys > MAX_KEYS)
         return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "more than %d key columns", MAX_KEYS);
     if (n_keys > 1 && partials)
@@ -422,22 +396,25 @@ int32_t groupby_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_col
     RowSource rs;
     rs.n_rows = n_rows;
     Stager stg{c, mem_space};
+    const size_t mbytes = (size_t)(n_rows + 7) / 8;
+    // a value column is read as 8-byte cells whatever its dtype
+    auto val_size = [&](const pandrs_hip_column &v) { return stg.in_size(v.data, size_t(n_rows) * 8) + stg.in_size(v.null_mask, mbytes); };
     if (mem_space == PANDRS_HIP_MEM_HOST && n_rows > 0) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
         size_t need = 0;
-        for (int k = 0; k < n_keys; k++) need += dtype_bytes(keys[k].dtype, n_rows) + (n_rows + 7) / 8 + 1024;
-        for (int s = 0; s < pl.n_src; s++) need += size_t(n_rows) * 8 + (n_rows + 7) / 8 + 1024;
+        for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
+        for (int s = 0; s < pl.n_src; s++) need += val_size(vals[pl.src_col[s]]);
         for (int a = 0; a < n_aggs; a++)
-            if (is_sorted_pass_op(aggs[a].op)) need += size_t(n_rows) * 8 + (n_rows + 7) / 8 + 1024;
-        ST_TRY(c->staging.ensure(need + (1 << 16), c->stream));
+            if (is_sorted_pass_op(aggs[a].op)) need += val_size(vals[aggs[a].col]);
+        ST_TRY(stg.reserve(need));
     }
-    rs.key = KeyDesc{stg.in(keys[0].data, dtype_bytes(keys[0].dtype, n_rows)),
-                     (const uint8_t *)stg.in(keys[0].null_mask, (n_rows + 7) / 8), nullptr, keys[0].dtype};
+    const ColView k0 = stg.col(keys[0], n_rows);
+    rs.key = KeyDesc{k0.data, k0.mask, nullptr, keys[0].dtype};
     for (int s = 0; s < pl.n_src; s++) {
         const pandrs_hip_column &v = vals[pl.src_col[s]];
         if (n_rows > 0 && !v.data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "value column %d has no data", pl.src_col[s]);
         rs.val_data[s] = stg.in(v.data, size_t(n_rows) * 8);
-        rs.val_null_bits[s] = (const uint8_t *)stg.in(v.null_mask, (n_rows + 7) / 8);
+        rs.val_null_bits[s] = (const uint8_t *)stg.in(v.null_mask, mbytes);
     }
     // Median columns: device views of the original columns (shared with the plan's sources when the
     // column is also aggregated otherwise)
@@ -453,7 +430,7 @@ int32_t groupby_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_col
         if (!med_data[a]) {
             if (n_rows > 0 && !vals[col].data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "value column %d has no data", col);
             med_data[a] = stg.in(vals[col].data, size_t(n_rows) * 8);
-            med_null[a] = (const uint8_t *)stg.in(vals[col].null_mask, (n_rows + 7) / 8);
+            med_null[a] = (const uint8_t *)stg.in(vals[col].null_mask, mbytes);
         }
     }
     if (stg.status) return stg.status;
@@ -490,6 +467,7 @@ int32_t groupby_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs
                               int64_t n_rows, int64_t *out_n_groups) {
     if (!c || !out_n_groups || n_rows < 0 || n_keys < 1 || !keys)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "groupby_indices: bad arguments");
+    ST_TRY(check_mem_space("groupby_indices", mem_space));
     if (n_keys > MAX_KEYS) return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "more than %d key columns", MAX_KEYS);
     ST_TRY(check_cols(keys, n_keys, "key", true));
     for (int k = 0; k < n_keys; k++)
@@ -504,11 +482,11 @@ int32_t groupby_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs
     if (mem_space == PANDRS_HIP_MEM_HOST && n_rows > 0) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
         size_t need = 0;
-        for (int k = 0; k < n_keys; k++) need += dtype_bytes(keys[k].dtype, n_rows) + (n_rows + 7) / 8 + 1024;
-        ST_TRY(c->staging.ensure(need + (1 << 16), c->stream));
+        for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
+        ST_TRY(stg.reserve(need));
     }
-    KeyDesc key{stg.in(keys[0].data, dtype_bytes(keys[0].dtype, n_rows)),
-                (const uint8_t *)stg.in(keys[0].null_mask, (n_rows + 7) / 8), nullptr, keys[0].dtype};
+    const ColView k0 = stg.col(keys[0], n_rows);
+    KeyDesc key{k0.data, k0.mask, nullptr, keys[0].dtype};
     if (stg.status) return stg.status;
     PackDesc pd{};
     if (n_keys > 1 && n_rows > 0) ST_TRY(pack_multi_key(c, stg, keys, n_keys, n_rows, key, pd));
@@ -584,51 +562,46 @@ int32_t key_hash_cells_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
                              int64_t n_rows, uint64_t *out_cells) {
     if (!c || !keys || n_keys < 1 || n_keys > MAX_KEYS || n_rows < 0 || (n_rows && !out_cells))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "key_hash_cells: bad arguments");
+    ST_TRY(check_mem_space("key_hash_cells", mem_space));
     ST_TRY(check_cols(keys, n_keys, "key", true));
     if (n_rows == 0) return 0;
     std::lock_guard<std::mutex> lock(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    Stager stg{c, mem_space};
-    uint64_t *dst = out_cells;
-    if (mem_space == PANDRS_HIP_MEM_HOST) {
-        size_t need = size_t(n_rows) * 8 + 4096;
-        for (int k = 0; k < n_keys; k++) need += dtype_bytes(keys[k].dtype, n_rows) + (n_rows + 7) / 8 + 1024;
-        ST_TRY(c->staging.ensure(need + (1 << 16), c->stream));
-        dst = c->staging.take<uint64_t>(n_rows);
-        if (!dst) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-    }
+    Stager stg{c, mem_space, mem_space};       // the cells go where the columns came from
+    size_t need = stg.out_size(out_cells, size_t(n_rows) * 8);
+    for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
+    ST_TRY(stg.reserve(need));
+    uint64_t *dst = stg.out(out_cells, size_t(n_rows) * 8);
     HashKeys hk{};
     hk.n_keys = n_keys;
     for (int k = 0; k < n_keys; k++) {
         if (!keys[k].data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "key column %d has no data", k);
-        hk.key[k] = KeyDesc{stg.in(keys[k].data, dtype_bytes(keys[k].dtype, n_rows)),
-                            (const uint8_t *)stg.in(keys[k].null_mask, (n_rows + 7) / 8), nullptr, keys[k].dtype};
+        const ColView v = stg.col(keys[k], n_rows);
+        hk.key[k] = KeyDesc{v.data, v.mask, nullptr, keys[k].dtype};
     }
     if (stg.status) return stg.status;
     hipLaunchKernelGGL(key_hash_cells_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, hk, n_rows, dst);
     HIP_TRY(hipGetLastError());
-    if (mem_space == PANDRS_HIP_MEM_HOST) HIP_TRY(hipMemcpyAsync(out_cells, dst, size_t(n_rows) * 8, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back(size_t(n_rows) * 8));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int32_t bytes_to_bitmap_entry(pandrs_hip_ctx *c, int32_t mem_space, const uint8_t *bytes, int64_t n, uint8_t *out) {
     if (!c || n < 0 || (n && (!bytes || !out))) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bytes_to_bitmap: bad arguments");
+    ST_TRY(check_mem_space("bytes_to_bitmap", mem_space));
     if (n == 0) return 0;
     std::lock_guard<std::mutex> lock(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    const uint8_t *src = bytes; uint8_t *dst = out;
     const size_t nb = (size_t)(n + 7) / 8;
-    if (mem_space == PANDRS_HIP_MEM_HOST) {
-        ST_TRY(c->staging.ensure((size_t)n + nb + 4096, c->stream));
-        uint8_t *d = c->staging.take<uint8_t>(n); dst = c->staging.take<uint8_t>(nb);
-        if (!d || !dst) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        HIP_TRY(hipMemcpyAsync(d, bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
-        src = d;
-    }
+    Stager stg{c, mem_space, mem_space};
+    ST_TRY(stg.reserve(stg.in_size(bytes, (size_t)n) + stg.out_size(out, nb)));
+    const uint8_t *src = (const uint8_t *)stg.in(bytes, (size_t)n);
+    uint8_t *dst = stg.out(out, nb);
+    if (stg.status) return stg.status;
     hipLaunchKernelGGL(bytes_to_bitmap_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, src, n, dst);
     HIP_TRY(hipGetLastError());
-    if (mem_space == PANDRS_HIP_MEM_HOST) HIP_TRY(hipMemcpyAsync(out, dst, nb, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back(nb));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -639,6 +612,7 @@ int32_t shuffle_split_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
     if (!c || !key || !out_counts || !out_n_rows || n_rows < 0 || n_payload < 0 || n_payload > 16 || (n_payload && !payload) ||
         n_ranks < 1 || n_ranks > 1024)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "shuffle_split: bad arguments");
+    ST_TRY(check_mem_space("shuffle_split", mem_space));
     ST_TRY(check_cols(key, 1, "key", true));
     for (int p = 0; p < n_payload; p++)
         if (payload[p].dtype != PANDRS_HIP_I64 && payload[p].dtype != PANDRS_HIP_F64 && payload[p].dtype != PANDRS_HIP_U32CODE)
@@ -655,12 +629,13 @@ int32_t shuffle_split_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
     Stager stg{c, mem_space};
     if (mem_space == PANDRS_HIP_MEM_HOST) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        size_t need = dtype_bytes(key->dtype, n_rows) + (n_rows + 7) / 8 + 1024;
-        for (int p = 0; p < n_payload; p++) need += dtype_bytes(payload[p].dtype, n_rows) + (n_rows + 7) / 8 + 1024;
-        ST_TRY(c->staging.ensure(need + (1 << 16), c->stream));
+        size_t need = stg.col_size(*key, n_rows);
+        for (int p = 0; p < n_payload; p++) need += stg.col_size(payload[p], n_rows);
+        ST_TRY(stg.reserve(need));
     }
     if (!key->data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "shuffle_split: key column has no data");
-    KeyDesc kd{stg.in(key->data, dtype_bytes(key->dtype, n_rows)), (const uint8_t *)stg.in(key->null_mask, (n_rows + 7) / 8), nullptr, key->dtype};
+    const ColView kv = stg.col(*key, n_rows);
+    KeyDesc kd{kv.data, kv.mask, nullptr, key->dtype};
     ST_TRY(c->work.ensure(engine_workspace_bytes(n_rows, 0, 0) + (1 << 20), c->stream));
     size_t out_bytes = Arena::padded(size_t(n_rows) * 8) + Arena::padded(size_t(n_rows)) + 4096;
     for (int p = 0; p < n_payload; p++) out_bytes += Arena::padded(size_t(n_rows) * 8) + Arena::padded(size_t(n_rows));
@@ -676,8 +651,9 @@ int32_t shuffle_split_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
     else HIP_TRY(hipMemsetAsync(r.key_null, 0, (size_t)n_rows, c->stream));
     for (int p = 0; p < n_payload; p++) {
         if (!payload[p].data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "shuffle_split: payload column %d has no data", p);
-        const void *d = stg.in(payload[p].data, dtype_bytes(payload[p].dtype, n_rows));
-        const uint8_t *m = (const uint8_t *)stg.in(payload[p].null_mask, (n_rows + 7) / 8);
+        const ColView pv = stg.col(payload[p], n_rows);
+        const void *d = pv.data;
+        const uint8_t *m = pv.mask;
         r.pay[p] = c->shuf.take<uint64_t>(n_rows);
         if (!r.pay[p]) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "shuffle arena too small");
         sa.mv[sa.n_move++] = MoveDesc{d, r.pay[p], payload[p].dtype == PANDRS_HIP_U32CODE ? 4 : 0, 0};
@@ -718,6 +694,11 @@ __global__ void unpack_records_kernel(const uint64_t *rec, int64_t n, int W, uin
     for (int s = 0; s < W - 2; s++) states[(size_t)s * n + i] = r[2 + s];
 }
 
+// the staging-arena scratch both merges unpack their records into: keys | key_null | states
+static size_t unpacked_records_size(int64_t n_rows, size_t n_state) {
+    return Stager::slot(size_t(n_rows) * 8) + Stager::slot(size_t(n_rows)) + Stager::slot(size_t(n_rows) * 8 * n_state);
+}
+
 int32_t groupby_merge_entry(pandrs_hip_ctx *c, int32_t mem_space, int32_t key_dtype,
                             const uint64_t *records,
                             int64_t n_rows, const int32_t *val_dtypes, int32_t n_vals,
@@ -725,6 +706,7 @@ int32_t groupby_merge_entry(pandrs_hip_ctx *c, int32_t mem_space, int32_t key_dt
                             int32_t n_aggs, int64_t *out_n_groups) {
     if (!c || !out_n_groups || n_rows < 0 || (n_rows && !records) || n_vals < 0 || n_aggs < 0)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "groupby_merge: bad arguments");
+    ST_TRY(check_mem_space("groupby_merge", mem_space));
     Plan pl;
     ST_TRY(build_plan(val_dtypes, val_has_nulls, n_vals, aggs, n_aggs, pl));
     if (pl.has_median)
@@ -735,18 +717,17 @@ int32_t groupby_merge_entry(pandrs_hip_ctx *c, int32_t mem_space, int32_t key_dt
     timings_begin(c);
     const size_t n_state = 1 + (size_t)pl.n_states, W = 2 + n_state;
     // staging arena: [records (host mode only)] keys | key_null | states
-    ST_TRY(c->staging.ensure(size_t(n_rows) * 8 * W * (mem_space == PANDRS_HIP_MEM_HOST ? 2 : 1) + size_t(n_rows) * 16 + (1 << 16), c->stream));
+    Stager stg{c, mem_space};
+    ST_TRY(stg.reserve(stg.in_size(records, size_t(n_rows) * 8 * W) + unpacked_records_size(n_rows, n_state)));
     RowSource rs;
     rs.n_rows = n_rows;
     if (n_rows > 0) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        Stager stg{c, mem_space};
         const uint64_t *drec = (const uint64_t *)stg.in(records, size_t(n_rows) * 8 * W);
+        uint64_t *dk = stg.scratch<uint64_t>(n_rows);
+        uint8_t *dn = stg.scratch<uint8_t>(n_rows);
+        uint64_t *ds = stg.scratch<uint64_t>(size_t(n_rows) * n_state);
         if (stg.status) return stg.status;
-        uint64_t *dk = c->staging.take<uint64_t>(n_rows);
-        uint8_t *dn = c->staging.take<uint8_t>(n_rows);
-        uint64_t *ds = c->staging.take<uint64_t>(size_t(n_rows) * n_state);
-        if (!dk || !dn || !ds) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
         hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream,
                            drec, n_rows, (int)W, dk, dn, ds);
         HIP_TRY(hipGetLastError());
@@ -1077,17 +1058,17 @@ int32_t groupby_merge_blocks_entry(pandrs_hip_ctx *c, int32_t key_dtype, const u
     HIP_TRY(hipSetDevice(c->device));
     timings_begin(c);
     const size_t n_state = 1 + (size_t)pl.n_states, W = 2 + n_state;
-    ST_TRY(c->staging.ensure(size_t(n_rows) * 8 * W + size_t(n_rows) * 16 + (size_t)(n_src + 1) * 8 + (1 << 16), c->stream));
+    Stager stg{c, PANDRS_HIP_MEM_HOST};         // (of the row offsets: the blocks themselves are device-resident and read in place)
+    ST_TRY(stg.reserve(stg.in_size(roff, (size_t)(n_src + 1) * 8) + unpacked_records_size(n_rows, n_state)));
     RowSource rs;
     rs.n_rows = n_rows;
     if (n_rows > 0) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        int64_t *d_off = c->staging.take<int64_t>((size_t)n_src + 1);
-        uint64_t *dk = c->staging.take<uint64_t>(n_rows);
-        uint8_t *dn = c->staging.take<uint8_t>(n_rows);
-        uint64_t *ds = c->staging.take<uint64_t>(size_t(n_rows) * n_state);
-        if (!d_off || !dk || !dn || !ds) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        HIP_TRY(hipMemcpyAsync(d_off, roff, (size_t)(n_src + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        const int64_t *d_off = (const int64_t *)stg.in(roff, (size_t)(n_src + 1) * 8);
+        uint64_t *dk = stg.scratch<uint64_t>(n_rows);
+        uint8_t *dn = stg.scratch<uint8_t>(n_rows);
+        uint64_t *ds = stg.scratch<uint64_t>(size_t(n_rows) * n_state);
+        if (stg.status) return stg.status;
         hipLaunchKernelGGL(unblock_records_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream,
                            blocks, d_off, (uint32_t)n_src, n_rows, (int)W, dk, dn, ds);
         HIP_TRY(hipGetLastError());
@@ -1106,6 +1087,7 @@ int32_t partials_split_entry(pandrs_hip_ctx *c, int32_t mem_space, int32_t n_ran
                              uint64_t *out_records, int64_t *out_counts) {
     if (!c || n_ranks < 1 || n_ranks > 1024 || !out_counts)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "partials_split: bad arguments");
+    ST_TRY(check_mem_space("partials_split", mem_space));
     std::lock_guard<std::mutex> lock(c->mu);
     GroupbyResult &res = c->gb;
     if (!res.valid || !res.partials) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no partials retained in this context");

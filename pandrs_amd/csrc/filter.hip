@@ -152,9 +152,7 @@ int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
                              int32_t out_mem_space, int64_t *out_idx, int64_t *out_count) {
     if (!c || !cond || n_rows < 0 || !out_count || (n_rows > 0 && !cond->data))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_indices: bad arguments");
-    if ((mem_space != PANDRS_HIP_MEM_HOST && mem_space != PANDRS_HIP_MEM_DEVICE) ||
-        (out_idx && out_mem_space != PANDRS_HIP_MEM_HOST && out_mem_space != PANDRS_HIP_MEM_DEVICE))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_indices: bad memory space");
+    ST_TRY(check_mem_space("filter_indices", mem_space, out_idx ? out_mem_space : PANDRS_HIP_MEM_DEVICE));    // (no output, no output space)
     if (cond->dtype != PANDRS_HIP_BOOLBITS)
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "filter_indices: the condition has dtype %d, expected BOOLBITS (Boolean)", cond->dtype);
     if (n_rows >= (int64_t(1) << 32))
@@ -179,32 +177,18 @@ int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
     f.n_selected = 0;
     if (n_rows == 0) { f.valid = true; return timings_end(c); }
 
-    const uint8_t *d_cond = static_cast<const uint8_t *>(cond->data), *d_null = cond->null_mask;
+    ColView cv{cond->data, cond->null_mask};
     int64_t *d_out = out_idx;
-    const bool stage_in = mem_space == PANDRS_HIP_MEM_HOST, stage_out = out_idx && out_mem_space == PANDRS_HIP_MEM_HOST;
-    if (stage_in || stage_out) {
+    Stager stg{c, mem_space, out_mem_space};
+    const size_t out_room = (size_t)n_rows * 8;         // (the count is not known yet: room for every row)
+    if (const size_t need = stg.col_size(*cond, n_rows) + stg.out_size(out_idx, out_room)) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        size_t need = 4096;
-        if (stage_in) need += Arena::padded(nbytes + 16) * (cond->null_mask ? 2 : 1);
-        if (stage_out) need += Arena::padded((size_t)n_rows * 8 + 16);      // (the count is not known yet: room for every row)
-        ST_TRY(c->staging.ensure(need, c->stream));
-        if (stage_in) {
-            uint8_t *p = c->staging.take<uint8_t>(nbytes + 16);
-            if (!p) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(p, cond->data, nbytes, hipMemcpyHostToDevice, c->stream));
-            d_cond = p;
-            if (cond->null_mask) {
-                uint8_t *m = c->staging.take<uint8_t>(nbytes + 16);
-                if (!m) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-                HIP_TRY(hipMemcpyAsync(m, cond->null_mask, nbytes, hipMemcpyHostToDevice, c->stream));
-                d_null = m;
-            }
-        }
-        if (stage_out) {
-            d_out = c->staging.take<int64_t>((size_t)n_rows + 2);
-            if (!d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        }
+        ST_TRY(stg.reserve(need));
+        cv = stg.col(*cond, n_rows);
+        d_out = stg.out(out_idx, out_room);
+        if (stg.status) return stg.status;
     }
+    const uint8_t *d_cond = static_cast<const uint8_t *>(cv.data), *d_null = cv.mask;
     {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
         const int64_t blocks = (n_tiles + FT_THREADS / 64 - 1) / (FT_THREADS / 64);
@@ -223,8 +207,8 @@ int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
     HIP_TRY(hipStreamSynchronize(c->stream));
     f.n_selected = total;
     f.valid = true;
-    if (stage_out && total) {
-        HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
+    if (stg.out_dev && total) {
+        ST_TRY(stg.copy_back((size_t)total * 8));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     c->timings.algorithmic_bytes = (int64_t)nbytes * (d_null ? 3 : 2) + (out_idx ? (int64_t)total * 8 : 0);
@@ -235,9 +219,7 @@ int32_t filter_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_
 int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pandrs_hip_column *src, int64_t n_src, uint64_t fill_bits,
                             int32_t out_mem_space, void *out) {
     if (!c || !src || n_src < 0) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_gather: bad arguments");
-    if ((src_mem_space != PANDRS_HIP_MEM_HOST && src_mem_space != PANDRS_HIP_MEM_DEVICE) ||
-        (out_mem_space != PANDRS_HIP_MEM_HOST && out_mem_space != PANDRS_HIP_MEM_DEVICE))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_gather: bad memory space");
+    ST_TRY(check_mem_space("filter_gather", src_mem_space, out_mem_space));
     if (src->dtype < PANDRS_HIP_I64 || src->dtype > PANDRS_HIP_BOOLBITS)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_gather: bad dtype %d (CELL64 is not a frame column type)", src->dtype);
     std::lock_guard<std::mutex> lock(c->mu);                    // one critical section: the selection and the staging live in the context
@@ -253,40 +235,25 @@ int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pand
     const size_t esz = elem_bytes(kind), sbytes = dtype_bytes(src->dtype, n_src), mbytes = (size_t)(n_src + 7) / 8;
     HIP_TRY(hipSetDevice(c->device));
     timings_begin(c);
-    const void *d_src = src->data;
-    const uint8_t *d_null = src->null_mask;
+    ColView sv{src->data, src->null_mask};
     void *d_out = out;
-    const bool stage_in = src_mem_space == PANDRS_HIP_MEM_HOST, stage_out = out_mem_space == PANDRS_HIP_MEM_HOST;
-    if (stage_in || stage_out) {
+    Stager stg{c, src_mem_space, out_mem_space};
+    if (const size_t need = stg.col_size(*src, n_src) + stg.out_size(out, (size_t)n * esz)) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        size_t need = 4096;
-        if (stage_in) need += Arena::padded(sbytes + 16) + (src->null_mask ? Arena::padded(mbytes + 16) : 0);
-        if (stage_out) need += Arena::padded((size_t)n * esz + 16);
-        ST_TRY(c->staging.ensure(need, c->stream));
-        if (stage_in) {
-            void *p = c->staging.take<uint8_t>(sbytes + 16);
-            if (!p) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(p, src->data, sbytes, hipMemcpyHostToDevice, c->stream));
-            d_src = p;
-            if (src->null_mask) {
-                uint8_t *m = c->staging.take<uint8_t>(mbytes + 16);
-                if (!m) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-                HIP_TRY(hipMemcpyAsync(m, src->null_mask, mbytes, hipMemcpyHostToDevice, c->stream));
-                d_null = m;
-            }
-        }
-        if (stage_out) {
-            d_out = c->staging.take<uint8_t>((size_t)n * esz + 16);
-            if (!d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        }
+        ST_TRY(stg.reserve(need));
+        sv = stg.col(*src, n_src);
+        d_out = stg.out(out, (size_t)n * esz);
+        if (stg.status) return stg.status;
     }
+    const void *d_src = sv.data;
+    const uint8_t *d_null = sv.mask;
     if (kind != 2 && (reinterpret_cast<uintptr_t>(d_src) & (esz - 1)))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "filter_gather: the column must be %zu-byte aligned", esz);
     {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_GATHER);
         ST_TRY(launch_compact(c, kind, d_src, d_null, fill_bits, d_out));
     }
-    if (stage_out) HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * esz, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back((size_t)n * esz));
     c->timings.algorithmic_bytes = (int64_t)(kind == 2 ? mbytes : sbytes) + (d_null ? (int64_t)mbytes : 0) + (int64_t)(mbytes + n * esz);
     ST_TRY(timings_end(c));
     HIP_TRY(hipStreamSynchronize(c->stream));

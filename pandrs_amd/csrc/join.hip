@@ -588,31 +588,13 @@ __global__ void append_unmatched_kernel(const uint8_t *rmatched, const uint32_t 
 }
 
 
-static int32_t stage_key(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n, KeyDesc *out) {
-    const void *d = col->data; const uint8_t *m = col->null_mask;
-    if (mem_space == PANDRS_HIP_MEM_HOST && n > 0) {
-        size_t bytes = dtype_bytes(col->dtype, n);
-        void *dd = c->staging.take<uint8_t>(bytes + 16);
-        if (!dd) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        HIP_TRY(hipMemcpyAsync(dd, d, bytes, hipMemcpyHostToDevice, c->stream));
-        d = dd;
-        if (m) {
-            uint8_t *dm = c->staging.take<uint8_t>((n + 7) / 8 + 16);
-            if (!dm) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(dm, m, (n + 7) / 8, hipMemcpyHostToDevice, c->stream));
-            m = dm;
-        }
-    }
-    *out = KeyDesc{d, m, nullptr, col->dtype};
-    return 0;
-}
-
 static int32_t join_core(pandrs_hip_ctx *c, const KeyDesc &lkey, int64_t nl, const KeyDesc &rkey, int64_t nr, int32_t how);
 
 int32_t join_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *lk, int64_t nl,
                    const pandrs_hip_column *rk, int64_t nr, int32_t how, int64_t *out_n) {
     if (!c || !lk || !rk || !out_n || nl < 0 || nr < 0 || how < PANDRS_HIP_JOIN_INNER || how > PANDRS_HIP_JOIN_OUTER)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join: bad arguments");
+    ST_TRY(check_mem_space("join", mem_space));
     if (lk->dtype != rk->dtype)                 // join.rs:98-104
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "join key columns have different types (%d and %d)", lk->dtype, rk->dtype);
     if (lk->dtype < PANDRS_HIP_I64 || lk->dtype > PANDRS_HIP_CELL64)
@@ -625,12 +607,14 @@ int32_t join_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column
     HIP_TRY(hipSetDevice(c->device));
     timings_begin(c);
     KeyDesc lkey{}, rkey{};
+    Stager stg{c, mem_space};
     {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        if (mem_space == PANDRS_HIP_MEM_HOST)
-            ST_TRY(c->staging.ensure(dtype_bytes(lk->dtype, nl) + dtype_bytes(rk->dtype, nr) + (nl + nr) / 8 + (1 << 16), c->stream));
-        ST_TRY(stage_key(c, mem_space, lk, nl, &lkey));
-        ST_TRY(stage_key(c, mem_space, rk, nr, &rkey));
+        ST_TRY(stg.reserve(stg.col_size(*lk, nl) + stg.col_size(*rk, nr)));
+        const ColView l = stg.col(*lk, nl), r = stg.col(*rk, nr);
+        if (stg.status) return stg.status;
+        lkey = KeyDesc{l.data, l.mask, nullptr, lk->dtype};
+        rkey = KeyDesc{r.data, r.mask, nullptr, rk->dtype};
     }
     ST_TRY(join_core(c, lkey, nl, rkey, nr, how));
     // B_join for index output: both key columns read once, 16 B per output row written
@@ -1526,6 +1510,9 @@ int32_t join_groupby_sum_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandr
                                int64_t nr, int64_t *out_n_groups) {
     if (!c || !lk || !lv || !rk || !rg || !out_n_groups || nl < 0 || nr < 0)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_groupby_sum: bad arguments");
+    ST_TRY(check_mem_space("join_groupby_sum", mem_space));
+    if ((nl && (!lk->data || !lv->data)) || (nr && (!rk->data || !rg->data)))
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_groupby_sum: a column has no data");
     if (lk->dtype != rk->dtype)
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "join key columns have different types (%d and %d)", lk->dtype, rk->dtype);
     if (lv->dtype != PANDRS_HIP_I64 && lv->dtype != PANDRS_HIP_F64)
@@ -1549,15 +1536,17 @@ int32_t join_groupby_sum_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandr
     timings_begin(c);
     c->jn.valid = false;
     KeyDesc lkey{}, rkey{}, lval{}, rgrp{};
+    Stager stg{c, mem_space};                   // (one per attempt: reserve() rewinds the arena)
     {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        if (mem_space == PANDRS_HIP_MEM_HOST)
-            ST_TRY(c->staging.ensure(dtype_bytes(lk->dtype, nl) + dtype_bytes(rk->dtype, nr) + size_t(nl) * 8 + size_t(nr) * 8 +
-                                     (nl + nr) / 2 + (1 << 16), c->stream));
-        ST_TRY(stage_key(c, mem_space, lk, nl, &lkey));
-        ST_TRY(stage_key(c, mem_space, rk, nr, &rkey));
-        ST_TRY(stage_key(c, mem_space, lv, nl, &lval));
-        ST_TRY(stage_key(c, mem_space, rg, nr, &rgrp));
+        ST_TRY(stg.reserve(stg.col_size(*lk, nl) + stg.col_size(*rk, nr) + stg.col_size(*lv, nl) + stg.col_size(*rg, nr)));
+        const pandrs_hip_column *cols[4] = {lk, rk, lv, rg};
+        KeyDesc *descs[4] = {&lkey, &rkey, &lval, &rgrp};
+        for (int i = 0; i < 4; i++) {
+            const ColView v = stg.col(*cols[i], i & 1 ? nr : nl);
+            *descs[i] = KeyDesc{v.data, v.mask, nullptr, cols[i]->dtype};
+        }
+        if (stg.status) return stg.status;
     }
     int64_t P = c->opt.partitions > 0 ? c->opt.partitions
                                      : std::max<int64_t>(1, (int64_t)std::ceil((double)nr / (JN_RCAP * 0.6)));

@@ -126,7 +126,8 @@ __global__ __launch_bounds__(RD_THREADS) void reduce_kernel(const uint64_t *data
 // All the statistics K1's three families of reference functions need (see pandrs_hip_reduce_stats in the header).
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                            pandrs_hip_column_stats *st) {
-    if (!c || !col || !st || n < 0) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce: bad arguments");
+    if (!c || !col || !st || n < 0 || (n > 0 && !col->data)) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce: bad arguments");
+    ST_TRY(check_mem_space("reduce", mem_space));
     if (col->dtype != PANDRS_HIP_I64 && col->dtype != PANDRS_HIP_F64)
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "reduce: dtype %d is not numeric", col->dtype);       // Error::Type (aggregate.rs:57)
     const bool f64 = col->dtype == PANDRS_HIP_F64;
@@ -135,21 +136,14 @@ int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
     timings_begin(c);
     int blocks = (int)std::min<int64_t>(RD_BLOCKS, std::max<int64_t>(1, (n / 2 + RD_THREADS * RD_VEC - 1) / (RD_THREADS * RD_VEC)));
     RedPartial *h = reinterpret_cast<RedPartial *>(c->pinned);
-    size_t need = Arena::padded(sizeof(RedPartial) * blocks) + (mem_space == PANDRS_HIP_MEM_HOST ? size_t(n) * 8 + (n + 7) / 8 + 4096 : 0) + 4096;
-    ST_TRY(c->work.ensure(need, c->stream));
+    ST_TRY(c->work.ensure(Arena::padded(sizeof(RedPartial) * blocks) + 4096, c->stream));
     RedPartial *dp = c->work.take<RedPartial>(blocks);
-    const uint64_t *data = (const uint64_t *)col->data;
-    const uint8_t *mask = col->null_mask;
-    if (mem_space == PANDRS_HIP_MEM_HOST && n > 0) {
-        uint64_t *dd = c->work.take<uint64_t>(n);
-        HIP_TRY(hipMemcpyAsync(dd, col->data, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
-        data = dd;
-        if (mask) {
-            uint8_t *dm = c->work.take<uint8_t>((n + 7) / 8);
-            HIP_TRY(hipMemcpyAsync(dm, mask, (n + 7) / 8, hipMemcpyHostToDevice, c->stream));
-            mask = dm;
-        }
-    }
+    Stager stg{c, mem_space};
+    ST_TRY(stg.reserve(stg.col_size(*col, n)));
+    const ColView v = stg.col(*col, n);
+    if (stg.status) return stg.status;
+    const uint64_t *data = (const uint64_t *)v.data;
+    const uint8_t *mask = v.mask;
     if (n > 0 && (reinterpret_cast<uintptr_t>(data) & 7))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce: the column must be 8-byte aligned");
     {
@@ -233,6 +227,7 @@ static int32_t gather_locked(pandrs_hip_ctx *c, int kind, const void *src, const
 int32_t gather_entry(pandrs_hip_ctx *c, int32_t mem_space, int kind, const void *src, const uint8_t *mask,
                      const int64_t *idx, int64_t n, uint64_t fill_bits, void *out, int64_t n_src, const int64_t *only_where_negative) {
     if (!c || n < 0 || (n && (!idx || !out))) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "gather: bad arguments");
+    ST_TRY(check_mem_space("gather", mem_space));
     if (n == 0) return 0;
     if (mem_space == PANDRS_HIP_MEM_HOST)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT,
@@ -266,6 +261,7 @@ int32_t gather_column_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
                             const int64_t *idx, int64_t n, uint64_t fill_bits, void *out) {
     if (!c || !src || n_src < 0 || n < 0 || (n && (!idx || !out)))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "gather_column: bad arguments");
+    ST_TRY(check_mem_space("gather_column", mem_space));
     if (src->dtype < PANDRS_HIP_I64 || src->dtype > PANDRS_HIP_BOOLBITS)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "gather_column: bad dtype %d", src->dtype);
     const int kind = src->dtype == PANDRS_HIP_U32CODE ? 1 : (src->dtype == PANDRS_HIP_BOOLBITS ? 2 : 0);
@@ -273,30 +269,7 @@ int32_t gather_column_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
     if (mem_space == PANDRS_HIP_MEM_DEVICE)
         return gather_entry(c, mem_space, kind, src->data, src->null_mask, idx, n, fill_bits, out, n_src);
     const size_t esz = kind == 0 ? 8 : (kind == 1 ? 4 : 1);
-    const void *d_src = nullptr; const uint8_t *d_mask = nullptr; int64_t *d_idx = nullptr; void *d_out = nullptr;
-    std::lock_guard<std::mutex> lock(c->mu);          // one critical section: the staged buffers live in the context
-    {
-        HIP_TRY(hipSetDevice(c->device));
-        const size_t sbytes = dtype_bytes(src->dtype, n_src), mbytes = (size_t)(n_src + 7) / 8;
-        ST_TRY(c->staging.ensure(sbytes + mbytes + size_t(n) * (8 + esz) + 4096, c->stream));
-        if (n_src > 0 && src->data) {
-            void *p = c->staging.take<uint8_t>(sbytes + 16);
-            if (!p) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(p, src->data, sbytes, hipMemcpyHostToDevice, c->stream));
-            d_src = p;
-            if (src->null_mask) {
-                uint8_t *m = c->staging.take<uint8_t>(mbytes + 16);
-                if (!m) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-                HIP_TRY(hipMemcpyAsync(m, src->null_mask, mbytes, hipMemcpyHostToDevice, c->stream));
-                d_mask = m;
-            }
-        }
-        d_idx = c->staging.take<int64_t>(n);
-        d_out = c->staging.take<uint8_t>(size_t(n) * esz + 16);
-        if (!d_idx || !d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        HIP_TRY(hipMemcpyAsync(d_idx, idx, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    if (!d_src) {                                   // empty source: every row takes the fill value
+    if (n_src == 0 || !src->data) {                 // empty source: every row takes the fill value
         for (int64_t i = 0; i < n; i++) {
             if (kind == 0) reinterpret_cast<uint64_t *>(out)[i] = fill_bits;
             else if (kind == 1) reinterpret_cast<uint32_t *>(out)[i] = (uint32_t)fill_bits;
@@ -304,8 +277,16 @@ int32_t gather_column_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_h
         }
         return 0;
     }
-    ST_TRY(gather_locked(c, kind, d_src, d_mask, d_idx, n, fill_bits, d_out, n_src, nullptr));
-    HIP_TRY(hipMemcpyAsync(out, d_out, size_t(n) * esz, hipMemcpyDeviceToHost, c->stream));
+    std::lock_guard<std::mutex> lock(c->mu);          // one critical section: the staged buffers live in the context
+    HIP_TRY(hipSetDevice(c->device));
+    Stager stg{c, mem_space, mem_space};
+    ST_TRY(stg.reserve(stg.col_size(*src, n_src) + stg.in_size(idx, size_t(n) * 8) + stg.out_size(out, size_t(n) * esz)));
+    const ColView s = stg.col(*src, n_src);
+    const int64_t *d_idx = (const int64_t *)stg.in(idx, size_t(n) * 8);
+    void *d_out = stg.out(out, size_t(n) * esz);
+    if (stg.status) return stg.status;
+    ST_TRY(gather_locked(c, kind, s.data, s.mask, d_idx, n, fill_bits, d_out, n_src, nullptr));
+    ST_TRY(stg.copy_back(size_t(n) * esz));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -319,65 +300,34 @@ int32_t join_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pandrs
                           uint64_t fill_bits, int32_t out_mem_space, void *out, const pandrs_hip_column *key_right, int64_t n_right) {
     if (!c || !src || n_src < 0 || (side != 0 && side != 1) || (key_right && (side != 0 || n_right < 0)))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_gather: bad arguments");
+    ST_TRY(check_mem_space("join_gather", src_mem_space, out_mem_space));
     if (src->dtype < PANDRS_HIP_I64 || src->dtype > PANDRS_HIP_BOOLBITS)
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_gather: bad dtype %d", src->dtype);
     if (key_right && key_right->dtype != src->dtype)
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "join_gather_key: the key columns have dtypes %d and %d", src->dtype, key_right->dtype);
     const int kind = src->dtype == PANDRS_HIP_U32CODE ? 1 : (src->dtype == PANDRS_HIP_BOOLBITS ? 2 : 0);
     const size_t esz = kind == 0 ? 8 : (kind == 1 ? 4 : 1);
-    struct Staged { const void *data; const uint8_t *mask; int64_t n; };
-    Staged s0{src->data, src->null_mask, n_src}, s1{key_right ? key_right->data : nullptr, key_right ? key_right->null_mask : nullptr, n_right};
-    const int64_t *d_left = nullptr, *d_right = nullptr;
-    void *d_out = out;
-    int64_t n = 0;
     // ONE critical section for the whole call: the retained pairs, the staged source and the staged output all live in the context,
     // and a concurrent call on the same context between two steps could replace any of them
     std::lock_guard<std::mutex> lock(c->mu);
-    {
-        if (!c->jn.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no join result retained in this context");
-        n = c->jn.n_rows;
-        if (n == 0) return 0;
-        if (!out) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_gather: null output");
-        d_left = c->jn.left_idx; d_right = c->jn.right_idx;
-        HIP_TRY(hipSetDevice(c->device));
-        const bool stage_src = src_mem_space == PANDRS_HIP_MEM_HOST, stage_out = out_mem_space == PANDRS_HIP_MEM_HOST;
-        auto col_bytes = [&](const pandrs_hip_column *col, int64_t rows) { return Arena::padded(dtype_bytes(col->dtype, rows) + 16) + Arena::padded((size_t)(rows + 7) / 8 + 16); };
-        size_t need = 4096;
-        if (stage_src) need += col_bytes(src, n_src) + (key_right ? col_bytes(key_right, n_right) : 0);
-        if (stage_out) need += Arena::padded(size_t(n) * esz + 16);
-        if (stage_src || stage_out) ST_TRY(c->staging.ensure(need, c->stream));
-        auto stage = [&](const pandrs_hip_column *col, Staged &st) -> int32_t {
-            st.data = nullptr; st.mask = nullptr;
-            if (st.n <= 0 || !col->data) return 0;
-            const size_t sbytes = dtype_bytes(col->dtype, st.n), mbytes = (size_t)(st.n + 7) / 8;
-            void *p = c->staging.take<uint8_t>(sbytes + 16);
-            if (!p) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(p, col->data, sbytes, hipMemcpyHostToDevice, c->stream));
-            st.data = p;
-            if (col->null_mask) {
-                uint8_t *m = c->staging.take<uint8_t>(mbytes + 16);
-                if (!m) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-                HIP_TRY(hipMemcpyAsync(m, col->null_mask, mbytes, hipMemcpyHostToDevice, c->stream));
-                st.mask = m;
-            }
-            return 0;
-        };
-        if (stage_src) {
-            ST_TRY(stage(src, s0));
-            if (key_right) ST_TRY(stage(key_right, s1));
-        }
-        if (stage_out) {
-            d_out = c->staging.take<uint8_t>(size_t(n) * esz + 16);
-            if (!d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        }
-    }
+    if (!c->jn.valid) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "no join result retained in this context");
+    const int64_t n = c->jn.n_rows;
+    if (n == 0) return 0;
+    if (!out) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "join_gather: null output");
+    const int64_t *d_left = c->jn.left_idx, *d_right = c->jn.right_idx;
+    HIP_TRY(hipSetDevice(c->device));
+    Stager stg{c, src_mem_space, out_mem_space};
+    ST_TRY(stg.reserve(stg.col_size(*src, n_src) + (key_right ? stg.col_size(*key_right, n_right) : 0) + stg.out_size(out, size_t(n) * esz)));
+    const ColView s0 = stg.col(*src, n_src), s1 = key_right ? stg.col(*key_right, n_right) : ColView{};
+    void *d_out = stg.out(out, size_t(n) * esz);
+    if (stg.status) return stg.status;
     // a source without rows is never dereferenced: the kernel's bounds test (n_src = 0) sends every row to the fill value
     ST_TRY(gather_locked(c, kind, s0.data ? s0.data : (const void *)d_left, s0.mask, side ? d_right : d_left, n, fill_bits, d_out,
-                         s0.data ? s0.n : 0, nullptr));
+                         s0.data ? n_src : 0, nullptr));
     if (key_right)
-        ST_TRY(gather_locked(c, kind, s1.data ? s1.data : (const void *)d_left, s1.mask, d_right, n, fill_bits, d_out, s1.data ? s1.n : 0,
+        ST_TRY(gather_locked(c, kind, s1.data ? s1.data : (const void *)d_left, s1.mask, d_right, n, fill_bits, d_out, s1.data ? n_right : 0,
                              /*only_where_negative=*/d_left));
-    if (out_mem_space == PANDRS_HIP_MEM_HOST) HIP_TRY(hipMemcpyAsync(out, d_out, size_t(n) * esz, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back(size_t(n) * esz));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

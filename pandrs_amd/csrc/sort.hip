@@ -298,9 +298,7 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
                            int32_t out_mem_space, int64_t *out_idx) {
     if (!c || !keys || n_keys <= 0 || n_rows < 0 || n_codes < 0 || (n_rows > 0 && !out_idx))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: bad arguments");
-    if ((mem_space != PANDRS_HIP_MEM_HOST && mem_space != PANDRS_HIP_MEM_DEVICE) ||
-        (out_mem_space != PANDRS_HIP_MEM_HOST && out_mem_space != PANDRS_HIP_MEM_DEVICE))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: bad memory space");
+    ST_TRY(check_mem_space("sort_indices", mem_space, out_mem_space));
     if (n_rows >= (int64_t(1) << 32))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: %lld rows; one call takes fewer than 2^32", (long long)n_rows);
     bool any_string = false;
@@ -321,41 +319,23 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
 
     // ---- host columns (and the rank table with them) are staged; device columns are read in place ----
     std::vector<SortKeyDesc> kd(n_keys);
-    int64_t *d_out = out_idx;
+    int64_t *d_out = nullptr;
+    Stager stg{c, mem_space, out_mem_space};
     {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        const bool host = mem_space == PANDRS_HIP_MEM_HOST;
-        size_t need = 4096;
-        if (host) {
-            for (int k = 0; k < n_keys; k++)
-                need += Arena::padded(dtype_bytes(keys[k].dtype, n_rows) + 16) + (keys[k].null_mask ? Arena::padded(n / 8 + 17) : 0);
-            if (any_string) need += Arena::padded((size_t)n_codes * 4 + 16);
-        }
-        if (out_mem_space == PANDRS_HIP_MEM_HOST) need += Arena::padded(n * 8 + 16);
-        ST_TRY(c->staging.ensure(need, c->stream));
-        auto stage = [&](const void *p, size_t bytes, const void **out) -> int32_t {
-            *out = p;
-            if (!host || !p) return 0;
-            void *d = c->staging.take<uint8_t>(bytes + 16);
-            if (!d) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, c->stream));
-            *out = d;
-            return 0;
-        };
-        const void *d_rank = nullptr;
-        if (any_string) ST_TRY(stage(code_rank, (size_t)n_codes * 4, &d_rank));
+        const size_t rank_bytes = any_string ? (size_t)n_codes * 4 : 0;
+        size_t need = stg.in_size(code_rank, rank_bytes) + stg.out_size(out_idx, n * 8);
+        for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
+        ST_TRY(stg.reserve(need));
+        const void *d_rank = stg.in(code_rank, rank_bytes);
         for (int k = 0; k < n_keys; k++) {
-            const void *data, *mask;
-            ST_TRY(stage(keys[k].data, dtype_bytes(keys[k].dtype, n_rows), &data));
-            ST_TRY(stage(keys[k].null_mask, (n + 7) / 8, &mask));
-            kd[k].key = KeyDesc{data, (const uint8_t *)mask, nullptr, keys[k].dtype};
+            const ColView v = stg.col(keys[k], n_rows);
+            kd[k].key = KeyDesc{v.data, v.mask, nullptr, keys[k].dtype};
             kd[k].rank = keys[k].dtype == PANDRS_HIP_U32CODE ? (const uint32_t *)d_rank : nullptr;
             kd[k].n_codes = (uint64_t)n_codes;
         }
-        if (out_mem_space == PANDRS_HIP_MEM_HOST) {
-            d_out = c->staging.take<int64_t>(n + 2);
-            if (!d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        }
+        d_out = stg.out(out_idx, n * 8);
+        if (stg.status) return stg.status;
     }
 
     // ---- code widths: one min / max pass per key, one read-back for all ----
@@ -520,8 +500,7 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
         c->timings.algorithmic_bytes = alg;
         c->timings.n_partitions = (int64_t)plan.size();
     }
-    if (out_mem_space == PANDRS_HIP_MEM_HOST)
-        HIP_TRY(hipMemcpyAsync(out_idx, d_out, n * 8, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back(n * 8));
     ST_TRY(timings_end(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

@@ -571,9 +571,7 @@ int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_colu
                      const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out) {
     if (!c || !col || !spec || n_rows < 0 || (n_rows > 0 && (!col->data || !out)))
         return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "window: bad arguments");
-    if ((mem_space != PANDRS_HIP_MEM_HOST && mem_space != PANDRS_HIP_MEM_DEVICE) ||
-        (out_mem_space != PANDRS_HIP_MEM_HOST && out_mem_space != PANDRS_HIP_MEM_DEVICE))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "window: bad memory space");
+    ST_TRY(check_mem_space("window", mem_space, out_mem_space));
     if (col->dtype != PANDRS_HIP_I64 && col->dtype != PANDRS_HIP_F64)
         return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "window: the column has dtype %d, expected I64 or F64", col->dtype);
     const pandrs_hip_window_spec sp = *spec;
@@ -598,33 +596,18 @@ int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_colu
     const bool has_null = col->null_mask != nullptr;
     // ---- every buffer sized up front ----
     ST_TRY(c->win.ensure(window_workspace_bytes(sp, n, has_null), c->stream));
-    const void *d_data = col->data;
-    const uint8_t *d_null = col->null_mask;
+    ColView cv{col->data, col->null_mask};
     double *d_out = out;
-    const bool stage_in = mem_space == PANDRS_HIP_MEM_HOST, stage_out = out_mem_space == PANDRS_HIP_MEM_HOST;
-    if (stage_in || stage_out) {
+    Stager stg{c, mem_space, out_mem_space};
+    if (const size_t need = stg.col_size(*col, n) + stg.out_size(out, dbytes)) {
         PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        size_t need = 4096;
-        if (stage_in) need += Arena::padded(dbytes + 16) + (has_null ? Arena::padded(mbytes + 16) : 0);
-        if (stage_out) need += Arena::padded(dbytes + 16);
-        ST_TRY(c->staging.ensure(need, c->stream));
-        if (stage_in) {
-            void *p = c->staging.take<uint8_t>(dbytes + 16);
-            if (!p) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-            HIP_TRY(hipMemcpyAsync(p, col->data, dbytes, hipMemcpyHostToDevice, c->stream));
-            d_data = p;
-            if (has_null) {
-                uint8_t *m = c->staging.take<uint8_t>(mbytes + 16);
-                if (!m) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-                HIP_TRY(hipMemcpyAsync(m, col->null_mask, mbytes, hipMemcpyHostToDevice, c->stream));
-                d_null = m;
-            }
-        }
-        if (stage_out) {
-            d_out = c->staging.take<double>((size_t)n + 2);
-            if (!d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "staging arena too small");
-        }
+        ST_TRY(stg.reserve(need));
+        cv = stg.col(*col, n);
+        d_out = stg.out(out, dbytes);
+        if (stg.status) return stg.status;
     }
+    const void *d_data = cv.data;
+    const uint8_t *d_null = cv.mask;
     if (reinterpret_cast<uintptr_t>(d_data) & 7) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "window: the column must be 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_out) & 7) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "window: the output must be 8-byte aligned");
     const WnPlan plan = plan_of(sp, n, has_null);
@@ -696,7 +679,7 @@ int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_colu
             ST_TRY(ts_run(c, EwmVarOp{wc, sp.alpha, tc, d_out, sp.op == PANDRS_HIP_WINDOW_VAR}, n, agg1, car1));
         }
     }
-    if (stage_out) HIP_TRY(hipMemcpyAsync(out, d_out, dbytes, hipMemcpyDeviceToHost, c->stream));
+    ST_TRY(stg.copy_back(dbytes));
     c->timings.algorithmic_bytes = 2 * (int64_t)dbytes + (has_null ? (int64_t)mbytes : 0);     // the column (+ mask) in, the result out
     ST_TRY(timings_end(c));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -483,3 +483,89 @@ def test_in_library_exchange_with_real_ranks_over_a_host_transport(tmp_path, wor
         assert int(p["gb_allocs_in_steady_state"][0]) == 0 and int(p["join_allocs_in_steady_state"][0]) == 0
         assert int(p["failure_status"][0]) != 0                     # every rank, not only the failing one
     assert sum(int(p["after_failure_groups"][0]) for p in parts) == want[0].shape[1]
+
+
+def test_a_memory_space_that_is_neither_host_nor_device_is_invalid_at_every_entry_point(cctx):
+    """include/pandrs_hip.h, Conventions: a mem_space / out_mem_space other than PANDRS_HIP_MEM_HOST / _DEVICE is
+    PANDRS_HIP_ERR_INVALID_ARGUMENT at EVERY function that takes one, the fetches and the in-library exchange included,
+    and the context answers normally afterwards.  Every buffer handed over is device-resident: an entry point that read
+    the value as "device" would run on valid memory and fail this test on its status."""
+    import ctypes as C
+    import torch
+    from pandrs_amd import _lib as L
+    lib, h, comm, BAD, DEV = cctx.lib, cctx.h, cctx.comm, 2, L.MEM_DEVICE
+    rng = np.random.default_rng(21)
+    n = 4096
+    ids = rng.integers(0, 50, n).astype(np.int64)
+    keep = []
+    col = lambda a, dt: cctx._cols([(_dev(a), None, dt)], keep)[0]
+    k, v = col(ids, O.I64), col(rng.normal(size=n), O.F64)
+    code = col(ids.astype(np.uint32).view(np.int32), O.U32CODE)
+    cond = col(np.packbits(rng.random(n) < 0.5, bitorder="little"), O.BOOLBITS)
+    idx, rank = _dev(rng.integers(0, n, n).astype(np.int64)), _dev(np.arange(50, dtype=np.int32))
+    buf = torch.zeros(1 << 20, dtype=torch.int64, device="cuda:0")      # room for any output of these calls
+    torch.cuda.synchronize()                    # the library's stream does not wait for torch's
+    out = buf.data_ptr()
+    outs = (C.c_void_p * 1)(out)
+    agg = cctx._aggs([(0, O.SUM)])
+    ng, ns, cnt = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+    counts = (C.c_int64 * 2)()
+    f64_dt, no_nulls = (C.c_int32 * 1)(O.F64), (C.c_uint8 * 1)(0)
+    four, stats = (C.c_double * 4)(), L.ColumnStats()
+    s, q = C.c_double(0), C.c_double(0)
+    spec = L.WindowSpec(kind=L.WINDOW_KIND_ROLLING, op=L.WINDOW_MEAN, window=3, min_periods=-1, center=0, reserved=0, ddof=1, alpha=0.0)
+    # what the fetches, the gathers through retained results and partials_split read: retained by valid device calls
+    valid = [
+        ("groupby_indices", lambda sp: lib.pandrs_hip_groupby_indices(h, sp, k, 1, n, C.byref(ng))),
+        ("shuffle_split", lambda sp: lib.pandrs_hip_shuffle_split(h, sp, k, v, 1, n, 2, 0, counts, C.byref(cnt))),
+        ("join_indices", lambda sp: lib.pandrs_hip_join_indices(h, sp, k, 64, k, 64, O.INNER, C.byref(ng))),
+        ("filter_indices", lambda sp: lib.pandrs_hip_filter_indices(h, sp, cond, n, DEV, out, C.byref(cnt))),
+        ("groupby_agg", lambda sp: lib.pandrs_hip_groupby_agg(h, sp, k, 1, n, v, 1, agg, 1, C.byref(ng))),
+    ]
+    for name, call in valid:
+        assert call(DEV) == 0, (name, L.last_error())
+    bad = [(name, lambda call=call: call(BAD)) for name, call in valid] + [
+        ("groupby_fetch", lambda: lib.pandrs_hip_groupby_fetch(h, BAD, outs, None, None)),
+        ("groupby_indices_fetch", lambda: lib.pandrs_hip_groupby_indices_fetch(h, BAD, outs, None, None, None)),
+        ("shuffle_fetch", lambda: lib.pandrs_hip_shuffle_fetch(h, BAD, out, None, None, None)),
+        ("join_fetch", lambda: lib.pandrs_hip_join_fetch(h, BAD, out, None)),
+        ("join_gather src", lambda: lib.pandrs_hip_join_gather(h, BAD, v, n, 0, 0, DEV, out)),
+        ("join_gather out", lambda: lib.pandrs_hip_join_gather(h, DEV, v, n, 0, 0, BAD, out)),
+        ("join_gather_key src", lambda: lib.pandrs_hip_join_gather_key(h, BAD, k, 64, k, 64, 0, DEV, out)),
+        ("join_gather_key out", lambda: lib.pandrs_hip_join_gather_key(h, DEV, k, 64, k, 64, 0, BAD, out)),
+        ("filter_indices out", lambda: lib.pandrs_hip_filter_indices(h, DEV, cond, n, BAD, out, C.byref(cnt))),
+        ("filter_gather src", lambda: lib.pandrs_hip_filter_gather(h, BAD, v, n, 0, DEV, out)),
+        ("filter_gather out", lambda: lib.pandrs_hip_filter_gather(h, DEV, v, n, 0, BAD, out)),
+        ("key_hash_cells", lambda: lib.pandrs_hip_key_hash_cells(h, BAD, k, 1, n, out)),
+        ("bytes_to_bitmap", lambda: lib.pandrs_hip_bytes_to_bitmap(h, BAD, cond[0].data, n // 8, out)),
+        ("gather_i64", lambda: lib.pandrs_hip_gather_i64(h, BAD, k[0].data, None, idx.data_ptr(), n, 0, out)),
+        ("gather_f64", lambda: lib.pandrs_hip_gather_f64(h, BAD, v[0].data, None, idx.data_ptr(), n, 0.0, out)),
+        ("gather_u32", lambda: lib.pandrs_hip_gather_u32(h, BAD, code[0].data, None, idx.data_ptr(), n, 0, out)),
+        ("gather_bool", lambda: lib.pandrs_hip_gather_bool(h, BAD, cond[0].data, None, idx.data_ptr(), n, 0, out)),
+        ("gather_column", lambda: lib.pandrs_hip_gather_column(h, BAD, v, n, idx.data_ptr(), n, 0, out)),
+        ("join_groupby_sum", lambda: lib.pandrs_hip_join_groupby_sum(h, BAD, k, v, n, k, k, 64, C.byref(ng))),
+        ("sort_indices", lambda: lib.pandrs_hip_sort_indices(h, BAD, code, 1, None, rank.data_ptr(), 50, n, DEV, out)),
+        ("sort_indices out", lambda: lib.pandrs_hip_sort_indices(h, DEV, code, 1, None, rank.data_ptr(), 50, n, BAD, out)),
+        ("window", lambda: lib.pandrs_hip_window(h, BAD, v, n, C.byref(spec), DEV, out)),
+        ("window out", lambda: lib.pandrs_hip_window(h, DEV, v, n, C.byref(spec), BAD, out)),
+        ("reduce_column", lambda: lib.pandrs_hip_reduce_column(h, BAD, v, n, four, C.byref(cnt))),
+        ("reduce_moments", lambda: lib.pandrs_hip_reduce_moments(h, BAD, v, n, C.byref(s), C.byref(q), C.byref(cnt))),
+        ("reduce_stats", lambda: lib.pandrs_hip_reduce_stats(h, BAD, v, n, C.byref(stats))),
+        ("groupby_merge", lambda: lib.pandrs_hip_groupby_merge(h, BAD, O.I64, out, 16, f64_dt, 1, no_nulls, agg, 1, C.byref(ng))),
+        ("dist_groupby_agg", lambda: lib.pandrs_hip_dist_groupby_agg(h, comm, BAD, k, 1, n, v, 1, agg, 1, C.byref(ng))),
+        ("dist_join_groupby_sum", lambda: lib.pandrs_hip_dist_join_groupby_sum(h, comm, BAD, k, v, n, k, k, 64, C.byref(ng))),
+        # (last: the partials replace the retained groupby result)
+        ("groupby_partials", lambda: lib.pandrs_hip_groupby_partials(h, BAD, k, 1, n, v, 1, agg, 1, C.byref(ng), C.byref(ns))),
+    ]
+    for name, call in bad:
+        assert call() == L.ERR_INVALID_ARGUMENT, (name, L.last_error())
+        # (the status of the memory-space check, not of another: the exchange's join, device shards only, words its own)
+        assert "bad memory space 2" in L.last_error() or name == "dist_join_groupby_sum", (name, L.last_error())
+    assert lib.pandrs_hip_groupby_partials(h, DEV, k, 1, n, v, 1, agg, 1, C.byref(ng), C.byref(ns)) == 0
+    assert lib.pandrs_hip_partials_split(h, BAD, 2, out, counts) == L.ERR_INVALID_ARGUMENT, L.last_error()
+    assert "partials_split: bad memory space 2" in L.last_error()
+    assert lib.pandrs_hip_partials_split(h, DEV, 2, out, counts) == 0
+    # the context is as usable as before
+    keys, vals = [(ids, None, O.I64)], [(rng.normal(size=n), None, O.F64)]
+    assert_groupby_equal(cctx.groupby_agg(keys, n, vals, [(0, O.SUM), (0, O.COUNT)]),
+                         O.groupby_agg(keys, n, vals, [(0, O.SUM), (0, O.COUNT)]), [O.I64], int_exact_rows=[1])

@@ -832,6 +832,78 @@ def test_gpu_config_is_honoured():
         pa.Context(0).close()        # resets the limit
 
 
+def test_use_pinned_memory_covers_every_host_staged_family():
+    """pandrs_hip_config.use_pinned_memory page-locks the host columns of EVERY MEM_HOST call (include/pandrs_hip.h), not
+    of the groupby family alone: one call per other family on host columns of at least 1 MiB, against the reference its own
+    test file uses, and the same calls without a config give bit-identical results."""
+    import ctypes as C
+    import pandrs_amd as pa
+    from pandrs_amd import _lib as L
+    from tests import test_gpu_filter as TF, test_gpu_sort as TS, test_gpu_window as TW
+    lib = L.load()
+    rng = np.random.default_rng(23)
+    nl, nr = 300_000, 200_000                               # 2.4 MB / 1.6 MB of i64 keys
+    lk = (rng.integers(0, 150_000, nl).astype(np.int64), None, O.I64)
+    rk = (rng.integers(0, 150_000, nr).astype(np.int64), O.pack_mask(rng.random(nr) < 0.01), O.I64)
+    rv = (rng.normal(size=nr), O.pack_mask(rng.random(nr) < 0.2), O.F64)
+    n_idx = 250_000
+    idx = rng.integers(-1, nr, n_idx).astype(np.int64)      # (-1: no row, the fill value)
+    stats_col = (rng.normal(5, 2, 1_000_003), O.pack_mask(rng.random(1_000_003) < 0.2), O.F64)
+    names = TS.Col(L.U32CODE, rng.integers(0, len(TS.STRINGS), 400_000).astype(np.uint32), rng.random(400_000) < 0.1, TS.STRINGS)
+    n_f = 9_000_000                                         # a 1.1 MB BOOLBITS condition
+    cond_v, cond_nulls, cond = TF.cond_of(rng, n_f, 0.3, 0.1)
+    src_v, src_nulls, src = TF.src_of(rng, L.F64, n_f, 0.1)
+    n_w = 200_000
+    x, x_valid = TW.data_of(rng, n_w, 0.1)
+
+    def calls(c):
+        r = {}
+        r["li"], r["ri"] = c.join_indices(lk, nl, rk, nr, O.LEFT)
+        r["joined"] = c.join_gather(rv, nr, len(r["ri"]), 1, fill=-1.0)
+        out = np.empty(n_idx, np.float64)
+        col = (L.Column * 1)()
+        col[0].data, col[0].null_mask, col[0].dtype = rv[0].ctypes.data, rv[1].ctypes.data, O.F64
+        st = lib.pandrs_hip_gather_column(c.h, L.MEM_HOST, col, nr, idx.ctypes.data, n_idx, int(np.float64(-1.0).view(np.uint64)),
+                                          out.ctypes.data)
+        assert st == 0, L.last_error()
+        r["gathered"] = out
+        r["stats"], r["k1"] = _k1_check(c, stats_col, 1_000_003)
+        r["order"] = TS.got(c, [names], [True])
+        rows, cnt = c.filter_indices(cond, n_f)
+        r["rows"] = rows.cpu().numpy()
+        r["kept"] = c.filter_gather(src, n_f, cnt, fill=-7.5)
+        r["rolled"] = TW.roll(c, TW.col_of(x, x_valid), n_w, 5, "mean")
+        return r
+
+    try:
+        cfg = L.Config(enabled=1, device_id=0, memory_limit=0, fallback_to_cpu=1, use_pinned_memory=1, min_size_threshold=0)
+        assert lib.pandrs_hip_init(C.byref(cfg)) == 0
+        c = pa.Context(0)
+        pinned = calls(c)
+        c.close()
+    finally:
+        lib.pandrs_hip_init(None)    # back to the library defaults
+        pa.Context(0).close()
+    wl, wr = O.join_indices(lk, nl, rk, nr, O.LEFT)
+    np.testing.assert_array_equal(pinned["li"], wl)
+    np.testing.assert_array_equal(pinned["ri"], wr)
+    np.testing.assert_array_equal(pinned["joined"], O.gather(rv[0], rv[1], wr, -1.0, O.F64))
+    np.testing.assert_array_equal(pinned["gathered"], O.gather(rv[0], rv[1], idx, -1.0, O.F64))
+    np.testing.assert_array_equal(pinned["order"], TS.ref_lexsort([names], [True]))
+    want_rows = TF.want_rows(cond_v, cond_nulls)
+    np.testing.assert_array_equal(pinned["rows"], want_rows)
+    assert TF.same_bits(pinned["kept"], TF.want_values(src_v, src_nulls, want_rows, L.F64, -7.5))
+    assert TW.same(pinned["rolled"], TW.rolling_ref(x, x_valid, 5, False, "mean"))
+    c = pa.Context(0)
+    try:
+        plain = calls(c)
+    finally:
+        c.close()
+    for name in ("li", "ri", "joined", "gathered", "order", "rows", "kept", "rolled"):
+        assert TF.same_bits(np.asarray(plain[name]), np.asarray(pinned[name])), name
+    assert plain["stats"] == pinned["stats"]
+
+
 # ---- group_by's own result: row -> group assignment (G1, grouping.rs:22-115) -------------------------
 def check_group_indices(ctx, keys, n):
     """Complete characterisation of the reference's HashMap<key, Vec<usize>>: the rows are a
