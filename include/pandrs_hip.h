@@ -207,7 +207,7 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *   "generic_aggregate" 1 = the descriptor-driven generic instantiation of the round-1 kernel
  *   "agg_depth"         register-ring depth of the lean aggregate (2..4; default 3)
  *   "agg_ablate"        experiments only: switch parts of the lean aggregate off (see experiments/agg2_ablate.py)
- *   "sort_digit_bits"   experiments only: widest radix digit of pandrs_hip_sort_indices, 4 ... 11 (0 = the default, 11;
+ *   "sort_digit_bits"   experiments only: widest radix digit of pandrs_hip_sort_indices, 4 ... 8 (0 = the default, 8;
  *                       experiments/sort_bench.py --digit-bits)
  *   "no_runs"           1 = never the clustered-rows (RUNS) instantiation
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
@@ -489,7 +489,12 @@ int32_t pandrs_hip_join_groupby_sum(pandrs_hip_ctx *ctx, int32_t mem_space,
  * PANDRS_HIP_ERR_OUT_OF_MEMORY.  Host key columns are staged; device / resident columns are read in place.  out_idx
  * (n_rows int64 row indices, the element type of the gathers) lives in out_mem_space.  The frame a sort returns is
  * select_rows_by_indices_impl (src/optimized/split_dataframe/select.rs:172-226): every column gathered through
- * out_idx with nulls as 0 / 0.0 / "" / false and no null masks (pandrs_hip_gather_column). */
+ * out_idx with nulls as 0 / 0.0 / "" / false and no null masks (pandrs_hip_gather_column).
+ * pandrs_hip_get_timings' n_partitions is the number of radix passes.  Each key becomes a code of bitlength(span + has_nan +
+ * has_null) bits, span = max - min of its order-preserving images: image - min ascending, max - image descending, NaN =
+ * span + 1, null = span + 1 + has_nan.  The codes are packed MSB-first, the last key at bit 0, into 64-bit words.  Per word,
+ * the bits from the lowest to the highest one that varies over the rows are cut into ceil(bits / D) digits of ceil(bits /
+ * digits) bits (D = 8, or "sort_digit_bits"); a digit takes a pass iff one of its bits varies.  All keys constant: 0 passes. */
 int32_t pandrs_hip_sort_indices(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
                                 const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
                                 int32_t out_mem_space, int64_t *out_idx);

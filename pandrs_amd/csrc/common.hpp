@@ -230,7 +230,7 @@ struct Options {
     int64_t no_small = 0;            // 1 = never take the two-launch small-call path (groupby.hip run_small)
     int64_t agg_v1 = 0;              // 1 = never use the lean persistent aggregate kernel (aggregate2.hip)
     int64_t agg_depth = 0;           // experiments: register-ring depth of aggregate2 (C2 profile)
-    int64_t sort_digit_bits = 0;     // experiments: widest radix digit of pandrs_hip_sort_indices (0 = default, 4 ... 11)
+    int64_t sort_digit_bits = 0;     // experiments: widest radix digit of pandrs_hip_sort_indices (0 = default, 4 ... 8)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
 

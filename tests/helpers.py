@@ -53,3 +53,15 @@ def assert_groupby_equal(got, want, key_dtypes, int_exact_rows=(), rtol=1e-9):
             nan_g, nan_w = np.isnan(ga[a]), np.isnan(wa[a])
             np.testing.assert_array_equal(nan_g, nan_w)
             np.testing.assert_allclose(ga[a][~nan_g], wa[a][~nan_w], rtol=rtol, atol=0)
+
+
+def filter_ref(values, nulls=None, src=None, src_nulls=None, fill=0):
+    """OptimizedDataFrame::filter restated (data_ops.rs:37-121): the rows whose condition is Some(true), ascending; with
+    `src` also that column compacted through them, null cells as `fill` (a bool column as one uint8 per row)."""
+    sel = np.asarray(values, bool) if nulls is None else np.asarray(values, bool) & ~np.asarray(nulls, bool)
+    rows = np.flatnonzero(sel).astype(np.int64)
+    if src is None:
+        return rows
+    src = np.asarray(src)
+    out = src[rows] if src_nulls is None else np.where(np.asarray(src_nulls, bool)[rows], np.asarray(fill, src.dtype), src[rows])
+    return rows, out.astype(np.uint8 if src.dtype == np.bool_ else src.dtype)

@@ -97,3 +97,20 @@ def test_exceptions_become_status_codes(lib):
     assert handle.pandrs_hip_ctx_set_option(None, b"test_throw", 3) == lib.ERR_COMPUTATION
     assert handle.pandrs_hip_ctx_set_option(None, b"test_throw", 4) in (lib.ERR_OUT_OF_MEMORY, lib.ERR_COMPUTATION)
     assert handle.pandrs_hip_ctx_set_option(None, b"test_throw", 0) == 0
+
+
+def test_sort_digit_bits_range_in_the_header_is_the_kernels():
+    """The header documents the range of "sort_digit_bits"; sort.hip clamps to [4, SORT_MAX_DIGIT] and sizes the scatter's
+    LDS (SORT_MAX_BUCKETS, the static_assert) for SORT_MAX_DIGIT.  The two must name the same numbers."""
+    src = open(os.path.join(ROOT, "pandrs_amd", "csrc", "sort.hip")).read()
+    max_digit = int(re.search(r"constexpr int SORT_MAX_DIGIT = (\d+);", src).group(1))
+    lo = int(re.search(r"std::clamp<int64_t>\(c->opt\.sort_digit_bits, (\d+), SORT_MAX_DIGIT\)", src).group(1))
+    assert re.search(r"c->opt\.sort_digit_bits \? .* : SORT_MAX_DIGIT;", src)        # 0 = the default = the widest
+    assert "SORT_MAX_BUCKETS = 1 << SORT_MAX_DIGIT" in src
+    header = open(os.path.join(ROOT, "include", "pandrs_hip.h")).read()
+    m = re.search(r'"sort_digit_bits"[^\n]*?(\d+) \.\.\. (\d+) \(0 = the default, (\d+)', header)
+    assert m, "the header no longer states the range of sort_digit_bits"
+    assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (lo, max_digit, max_digit)
+    common = open(os.path.join(ROOT, "pandrs_amd", "csrc", "common.hpp")).read()
+    m = re.search(r"sort_digit_bits = 0;[^\n]*?(\d+) \.\.\. (\d+)\)", common)
+    assert m and (int(m.group(1)), int(m.group(2))) == (lo, max_digit)

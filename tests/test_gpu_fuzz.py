@@ -44,3 +44,36 @@ def test_fuzz_slice_distributed_real_ranks():
     concatenated, equal the oracle on the whole frame."""
     out = _run("fuzz_dist.py", 3, 14, 5)
     assert "fuzz_dist done: world 3, 14 cases, 0 failing rank-cases" in out
+
+
+# experiments/fuzz_ops.py: sort, filter, window and their chains.  kind -> (cases, seed); tests/test_references.py runs the same
+# slices dry (no engine call) on a CPU-only box and asserts that every coverage line is above zero.
+FUZZ_OPS_SLICES = {"sort": (1120, 6001), "filter": (1200, 6002), "window": (920, 6003), "chain": (160, 6004)}
+
+
+def _run_ops(kind):
+    count, seed = FUZZ_OPS_SLICES[kind]
+    out = _run("fuzz_ops.py", count, seed, env={"FUZZ_KIND": kind, "FUZZ_DRY": "0", "FUZZ_FIRST": "0"})
+    assert "fuzz_ops done: %d cases, 0 failures" % count in out
+    assert "features not reached" not in out and "coverage (cases run):" in out
+
+
+def test_fuzz_ops_slice_sort():
+    """Layout-directed keys: every digit width from 1 to 8, one to four and more key words, codes of 65 bits and codes that
+    straddle a word, constant digits, all-null / all-NaN / constant keys, sort_digit_bits 0 and 4 ... 8; the permutation
+    equals ref_lexsort's (and ref_cmp's up to 20 000 rows) and the pass count equals the one derived from the header's rule."""
+    _run_ops("sort")
+
+
+def test_fuzz_ops_slice_filter():
+    _run_ops("filter")
+
+
+def test_fuzz_ops_slice_window():
+    _run_ops("window")
+
+
+def test_fuzz_ops_slice_chains():
+    """filter -> gather -> sort -> gather -> window, filter -> gather -> groupby, sort -> gather -> groupby of the now clustered
+    rows, sort -> gather -> window: every intermediate stays on the device, every stage is compared."""
+    _run_ops("chain")
