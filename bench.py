@@ -10,7 +10,10 @@ value columns, sum/mean/min/max over each (16 aggregates).  N > 1 is weak scalin
 holds its own 100 M-row shard; per step it pre-aggregates locally, exchanges the partial rows
 with ONE all-to-all (RCCL) keyed on hash(key) mod N, and merges the partitions it owns.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+with the `roofline` figures those steps themselves produced.  --full adds what takes runs of its own
+after the timed steps: the other single-GPU configurations, the CPU baselines and the static PMC
+traffic figure of profiles/.
 """
 import argparse
 import json
@@ -378,9 +381,12 @@ def main():
     ap.add_argument("--groups", type=int, default=1_000_000)
     ap.add_argument("--cols", type=int, default=4)
     ap.add_argument("--cpu-sample", type=int, default=16_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extra configs and the CPU baselines and report the static PMC "
+                         "traffic figure beside the headline (about half a minute more); a plain run does none of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra configs (north-star sum line, C3, C4 shard, C5 shard) reported beside the headline")
+                    help="with --full: skip the extra configs (north-star sum line, C3, C4 shard, C5 shard) reported beside the headline")
     ap.add_argument("--workload", choices=["groupby", "join", "c4"], default="groupby",
                     help="groupby = BASELINE config 2 (the headline line); join = config 5 shape "
                          "(probe --rows per GPU, build rows/10 per GPU, inner join -> groupby(g).sum(v)); "
@@ -489,6 +495,7 @@ def main():
         ms_per_step = dt / k * 1e3
         dev_ms = total_kernel_ms / k                    # hipEvent time of the pipeline on its stream
         achieved = bytes_alg / (dev_ms * 1e-3) / 1e9
+        traffic, traffic_source = pmc_traffic(n, g, ncol) if args.full and world == 1 else (None, None)
         phases = {p: v / k for p, v in sorted(phase_sum.items())}
         out = {
             "metric": "Mrows/sec groupby-agg", "value": n * world / (dt / k) / 1e6, "unit": "Mrows/s",
@@ -502,8 +509,7 @@ def main():
                        "rows_per_gpu": n, "groups": g, "value_cols": ncol, "aggregates": len(aggs),
                        "parallelism": "row-range shards + 1 RCCL all-to-all of partial records inside the library (pandrs_hip_dist_groupby_agg)" if world > 1 else "1 GPU"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc_traffic(n, g, ncol)[0] if world == 1 else None,
-                         "traffic_source": pmc_traffic(n, g, ncol)[1] if world == 1 else None,
+                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
                          "algorithmic_bytes": bytes_alg, "device_ms": dev_ms, "phase_ms": phases,
                          "note": "whole groupby pipeline (estimate+histogram+scan+scatter+aggregate) "
                                  "timed with hipEvents on the library stream; B = N(K+8C)+G(K+8A)"},
@@ -518,11 +524,11 @@ def main():
             out["roofline"]["wall_ms_last_step"] = dgb.last_timings.get("wall_ms")
             out["roofline"]["note"] = ("local partial aggregation + split + all-to-all + merge; device_ms = hipEvent time of the "
                                        "local and merge pipelines + wall time of the exchange; B = N(K+8C)+G(K+8A) per GPU")
-        if not args.no_extras and world == 1 and not c4:
+        if args.full and not args.no_extras and world == 1 and not c4:
             del keys, vals, key_cols, val_cols
             torch.cuda.empty_cache()
             out.update(extra_configs(torch, pa, ctx, device))
-        if not args.no_cpu_baseline and world == 1 and not c4:
+        if args.full and not args.no_cpu_baseline and world == 1 and not c4:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, g, ncol, aggs)
             out["cpu_baseline_parallel"] = cpu_baseline_parallel(min(n, 2 * args.cpu_sample), g, ncol, aggs)
             out["cpu_baseline_typed"] = cpu_baseline_typed(min(n, 3 * args.cpu_sample), g, ncol)
@@ -610,7 +616,7 @@ def bench_join(args, torch, pa, dist, rank, local_rank, world, device):
                             "phase_ms": {p: v / k for p, v in sorted(phases.items())}}}
         if djg is not None:
             res["roofline"]["wall_ms_last_step"] = djg.last_wall_ms
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_join(10_000_000, 1_000_000)
         emit(res)
     if dist is not None:

@@ -6,7 +6,7 @@
 set -e
 tag=$1; root=$GRAFT_REPO_ROOT; out=$root/gpurun_out/prof_$tag
 mkdir -p $out; cd /tmp; export TMPDIR=/tmp
-B="$root/bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 2"
+B="$root/bench.py --steps 10 --warmup 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $B > $out/bench_under_rocprof.json 2> $out/stats.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 $B > $out/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 $B > $out/write.log 2>&1
@@ -16,7 +16,7 @@ cp $(find $out/write -name "*counter_collection.csv" | head -1) $root/profiles/$
 tail -1 $out/bench_under_rocprof.json > $root/profiles/${tag}_bench_under_rocprof.json
 cd $root
 python3 experiments/pmc_traffic.py profiles/${tag}_pmc_fetch_counter_collection.csv profiles/${tag}_pmc_write_counter_collection.csv 12 100000000 1000000 4 > profiles/${tag}_pmc_traffic.json
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 tail -1 $out/bench.json > profiles/${tag}_bench.json
 mkdir -p gpurun_out/profiles_$tag; cp profiles/${tag}_* gpurun_out/profiles_$tag/
 python3 - <<PY

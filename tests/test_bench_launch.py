@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -96,3 +98,43 @@ def test_dump_outputs_samples_large_results_under_64_mb(tmp_path):
     key = a["group_key_hi32.npy"][0].astype(np.uint64) << np.uint64(32) | a["group_key_lo32.npy"][0].astype(np.uint64)
     assert np.array_equal(key, np.sort(keys[0])[a["group_rank.npy"].astype(np.int64)])
     assert np.array_equal(a["aggregates.npy"][3], key.astype(np.float64) + 3)
+
+
+FULL_ONLY = ("cpu_baseline", "cpu_baseline_parallel", "cpu_baseline_typed", "cpu_baseline_join", "north_star_sum", "c1_shape_100m",
+             "c2_skew_80_20", "c2_sorted", "c3", "c4_shard", "c4_one_gpu", "c5_shard", "c5_one_gpu", "join_indices_50m_5m", "c1")
+
+
+def test_full_is_an_option_and_off_by_default():
+    """--full is accepted (here by the rehearsal, which has nothing to add); without it a run reports no CPU baseline or extra."""
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--rows", "20000", "--groups", "500", "--cols", "2"]
+    env = {"PANDRS_BENCH_BACKEND": "gloo", "RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1"}
+    for argv in (small, small + ["--full"]):
+        p = _run(argv, dict(env, MASTER_PORT=str(_free_port())))
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        rec = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.strip()][-1])     # gloo prints a banner of its own first
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and not set(FULL_ONLY) & set(rec)
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone_and_full_adds_the_rest():
+    """On the device, at a small size: a plain run prints the headline and the roofline figures of its own timed steps and
+    nothing that takes a run of its own; --full (here without the extra configs, whose sizes are fixed at 100 M rows and
+    more) adds the CPU baselines beside the same headline fields."""
+    small = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "200000", "--groups", "5000", "--cols", "2", "--cpu-sample", "50000"]
+    recs = []
+    for argv in (small, small + ["--full", "--no-extras"]):
+        p = _run(argv, {})
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        recs.append(json.loads(lines[0]))
+    plain, full = recs
+    for rec in recs:
+        assert rec["metric"] == "Mrows/sec groupby-agg" and rec["unit"] == "Mrows/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "f64" and rec["steps"] == 3 and rec["warmup"] == 1 and "dry_run" not in rec
+        assert rec["ms_per_step"] > 0 and abs(rec["value"] - 200000 / rec["ms_per_step"] / 1e3) <= 1e-6 * rec["value"]
+        assert rec["roofline"]["device_ms"] > 0 and rec["roofline"]["phase_ms"]
+    assert not set(FULL_ONLY) & set(plain) and plain["roofline"]["traffic"] is None
+    assert set(full) - set(plain) == {"cpu_baseline", "cpu_baseline_parallel", "cpu_baseline_typed"}
+    for name in ("cpu_baseline", "cpu_baseline_parallel", "cpu_baseline_typed"):
+        assert full[name]["value"] > 0 and full[name]["unit"] == "Mrows/s"
