@@ -601,6 +601,58 @@ typedef struct pandrs_hip_window_spec {
 int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                           const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
 
+/* ---- describe and exact percentiles of one numeric column ------------------------------------------------------------------
+ * Replaces OptimizedDataFrame::describe / describe_all (src/optimized/split_dataframe/stats.rs:50-171) over stats::describe
+ * and percentile (src/stats/descriptive.rs:91-166, :169-200), and the quantile part that describe_gpu
+ * (src/stats/gpu.rs:240-316) leaves to a CPU sort.  The values are the column's non-null cells as f64 (`v as f64` for I64):
+ *   count            the non-null cells;
+ *   mean             sum / count (:102);
+ *   std              sqrt(sum (x - mean)^2 / (count - 1)), two passes (:107-108); count == 1 gives 0.0 / 0.0 = NaN;
+ *   min, max         sorted[0], sorted[count - 1] (:110-111);
+ *   percentile p     index = (p / 100.0) * (count - 1) as f64, lo = floor, hi = ceil; sorted[lo] when lo == hi, else
+ *                    sorted[lo] * (1.0 - w) + sorted[hi] * w with w = index - lo; p == 0 and p == 100 are the ends (:182-199).
+ * pandrs_hip_describe is pandrs_hip_quantiles at 25 / 50 / 75 plus the moments in one call: the column is read once per pass,
+ * not once per statistic.  How: no sort; a multi-rank most-significant-digit radix SELECT (describe.hip): one stream for
+ * the counts, the sum and the extreme order-preserving codes, then one stream per 8-bit digit of (code - min code) that
+ * varies, counting only the rows that still match a wanted rank's prefix; the first of them also carries sum (x - mean)^2.
+ * Geometry (tests read it): describe_tile_rows = 2048 rows per workgroup iteration, describe_blocks_per_cu = 4, grid =
+ * min(describe_blocks_per_cu x compute units, ceil(n_rows / describe_tile_rows)) workgroups striding over the tiles.
+ * Exactness: min, max and every percentile are bit for bit the reference's (the selected element is the element its sort
+ * puts at that rank, also for I64 values beyond 2^53; the interpolation is the reference's expression, FMA contraction
+ * off); count is exact; mean and std carry the bound of the other device sums: within 1e-9 relative of
+ * the reference's sequential fold.
+ * Deviations:
+ *  - NaN: the reference's `partial_cmp(..).unwrap()` (:99) panics on a NaN cell.  Here a NaN cell counts and orders after
+ *    every number, as in pandrs_hip_sort_indices: max, and every percentile whose rank reaches the NaN block, are NaN; min
+ *    is the smallest number (NaN when there is none); mean and std are NaN by arithmetic.
+ *  - Signed zero: the order is the order-preserving code's, -0.0 before +0.0 (the reference's comparison ties them and its
+ *    stable sort keeps row order), so a result that is zero may differ from the reference in its sign bit only.
+ *  - describe_all: the reference's `if let Ok` (stats.rs:157-171) leaves out a column on any error.  The mirrors leave out
+ *    only a column whose describe raises InvalidValue (count 0 or 1); a device or argument error surfaces.
+ * count == 0 (no row, or only nulls) is status OK with count 0 and NaN everywhere; the reference returns
+ * Err(InvalidValue) (:92-96) and the mirrors raise it.  The reference also fails for count == 1 (its confidence interval
+ * asks TDistribution::new(0.0), src/stats/distributions.rs:188-193: Err(InvalidValue)); the ABI answers such a column
+ * (std NaN), the mirrors raise.
+ * Host columns are staged; device and resident columns are read in place (data 8-byte aligned, 16-byte alignment not
+ * needed; a null mask at any byte offset, bits past n_rows ignored).  The workspace does not grow with n_rows (per-workgroup
+ * partials, 32 x 256 digit counts, the rank slots); staging: the host column.  A memory_limit below either is
+ * PANDRS_HIP_ERR_OUT_OF_MEMORY.  Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold:
+ * PANDRS_HIP_ERR_BELOW_THRESHOLD; a column that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a NULL pointer, n_rows >=
+ * 2^32, n_percentiles outside 1 .. 16, a percentile outside [0, 100] or NaN (:176-180): PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ * Out of scope: skewness, kurtosis, mode, confidence intervals and outliers of StatisticalSummary. */
+typedef struct pandrs_hip_describe_stats {
+    int64_t count;          /* non-null cells */
+    double mean, std, min, q1, median, q3, max;   /* NaN each when count == 0 */
+} pandrs_hip_describe_stats;
+
+int32_t pandrs_hip_describe(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                            pandrs_hip_describe_stats *out);
+
+/* percentile(sorted non-null values, p) for 1 .. 16 values of p in [0, 100], any order, repeats allowed; out[j] answers
+ * percentiles[j], out_count = the non-null cells.  percentiles / out / out_count are host pointers. */
+int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                             const double *percentiles, int32_t n_percentiles, double *out, int64_t *out_count);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

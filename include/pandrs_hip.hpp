@@ -8,6 +8,7 @@
 //                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272, data_ops.rs:15-121,
 //                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167;
 //                             rolling / expanding / ewm: src/dataframe/window.rs:13-160 (series/window.rs)
+//                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -45,7 +46,7 @@ struct Error : std::runtime_error {
     enum Kind { ColumnNotFound, ColumnTypeMismatch, OperationFailed, Computation, InvalidInput, DuplicateColumnName, InconsistentRowCount, Empty, Type, BelowThreshold, Index,
                 EmptyColumnList, InconsistentArrayLengths,     // sort.rs:147-149, :161-166
                 Format,                                        // select.rs:151-157 (select_by_mask's mask length)
-                InvalidValue };                                // series/window.rs:113-116, :567-573, dataframe/window.rs:62-67
+                InvalidValue };                                // series/window.rs:113-116, :567-573, dataframe/window.rs:62-67, stats/descriptive.rs:92-96
     Kind kind;
     Error(Kind k, const std::string &m) : std::runtime_error(m), kind(k) {}
 };
@@ -223,6 +224,12 @@ inline std::string key_string(int32_t dtype, uint64_t cell, bool is_null, const 
 }
 }  // namespace detail
 
+// StatDescribe (src/optimized/split_dataframe/stats.rs:13-19): count, mean, std, min, 25%, 50%, 75%, max
+struct StatDescribe {
+    std::unordered_map<std::string, double> stats;
+    std::vector<std::pair<std::string, double>> stats_list;    // the same, in that order
+};
+
 enum class AggregateOp { Sum = 0, Mean, Min, Max, Count, Std, Var, Median, First, Last, Custom,   // types.rs:11-34
                          Nunique };   // + the legacy AggFunc::Nunique (src/dataframe/groupby.rs:41)
 enum class JoinType { Inner = 0, Left, Right, Outer };                                              // join.rs:11-20
@@ -298,6 +305,42 @@ public:
     double mean(const std::string &name) const { auto s = non_empty(name); return s.sum_f64 / (double)s.count; }
     double min(const std::string &name) const { return non_empty(name).min; }
     double max(const std::string &name) const { return non_empty(name).max; }
+
+    // describe (stats.rs:50-151 over stats/descriptive.rs:91-200): count, mean, std (two passes, count - 1), min, the
+    // 25 / 50 / 75 percentiles (linear interpolation at (p / 100) * (count - 1)) and max of the non-null cells as f64, from
+    // one pandrs_hip_describe call (a radix select, no sort).  Errors before any device call: ColumnNotFound, Type (a
+    // String or Boolean column).  InvalidValue for a column without a non-null cell (descriptive.rs:92-96) and for one
+    // with a single non-null cell (the reference's confidence interval refuses 0 degrees of freedom,
+    // stats/distributions.rs:188-193).  NaN cells order after every number (pandrs_hip.h).
+    StatDescribe describe(const std::string &column_name) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");      // stats.rs:146-149
+        pandrs_hip_describe_stats st{};
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_describe(detail::context(), mem_space(), &v, (int64_t)row_count_, &st));
+        }
+        if (st.count == 0) throw Error(Error::InvalidValue, "Cannot compute statistics for empty data");
+        if (st.count == 1) throw Error(Error::InvalidValue, "Degrees of freedom must be positive");
+        StatDescribe d;
+        d.stats_list = {{"count", (double)st.count}, {"mean", st.mean}, {"std", st.std}, {"min", st.min},
+                        {"25%", st.q1}, {"50%", st.median}, {"75%", st.q3}, {"max", st.max}};                  // stats.rs:74-83
+        for (auto &kv : d.stats_list) d.stats[kv.first] = kv.second;
+        return d;
+    }
+    // describe_all (stats.rs:157-171): every Int64 / Float64 column; one whose describe fails with InvalidValue is left out
+    std::map<std::string, StatDescribe> describe_all() const {
+        std::map<std::string, StatDescribe> results;
+        for (size_t i = 0; i < columns.size(); i++) {
+            if (columns[i].index() > 1) continue;
+            try {
+                results.emplace(column_names[i], describe(column_names[i]));
+            } catch (const Error &e) {
+                if (e.kind != Error::InvalidValue) throw;
+            }
+        }
+        return results;
+    }
 
     // sort.rs:18-143 / :146-272: the rows ordered by by[0], then by[1], ... (ascending: one flag per column, empty =
     // all ascending).  Stable, also descending; nulls last in both directions; strings in byte-wise order; NaN after

@@ -482,6 +482,21 @@ int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_h
     return pandrs::window_entry(ctx, mem_space, col, n_rows, spec, out_mem_space, out);
 } catch (...) { return pandrs::on_exception("pandrs_hip_window"); }
 
+int32_t pandrs_hip_describe(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                            pandrs_hip_describe_stats *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "describe: no context");
+    if (!out) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "describe: null output");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::describe_entry(ctx, mem_space, col, n_rows, nullptr, 0, nullptr, nullptr, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_describe"); }
+
+int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                             const double *percentiles, int32_t n_percentiles, double *out, int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "quantiles: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::describe_entry(ctx, mem_space, col, n_rows, percentiles, n_percentiles, out, out_count, nullptr);
+} catch (...) { return pandrs::on_exception("pandrs_hip_quantiles"); }
+
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {
     if (!out_sum || !out_sum_sq || !out_count) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce_moments: bad arguments");

@@ -375,6 +375,9 @@ int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pand
 size_t filter_workspace_bytes(int64_t n_rows);
 int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                      const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
+// describe.hip: out_stats != nullptr = describe (25 / 50 / 75 and the moments), else the caller's percentiles
+int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *percentiles,
+                       int32_t n_percentiles, double *out_q, int64_t *out_count, pandrs_hip_describe_stats *out_stats);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

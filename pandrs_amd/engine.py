@@ -768,3 +768,32 @@ class Context:
         if st:
             _raise(st)
         return out[:n] if out_device else out
+
+    # -- describe / exact percentiles (radix select) -------------------------------------------------------------
+    def describe(self, col, n_rows):
+        """count, mean, std, min, 25%, 50%, 75%, max of one I64 / F64 column on the device (pandrs_hip_describe;
+        OptimizedDataFrame::describe, split_dataframe/stats.rs:50-151 over stats/descriptive.rs:91-200).  `col` is a
+        (data, mask, dtype) triple on the host or the device, or a ResidentColumn.  -> dict with the fields of
+        pandrs_hip_describe_stats (count, mean, std, min, q1, median, q3, max); count 0 gives NaN everywhere."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        out = L.DescribeStats()
+        st = self.lib.pandrs_hip_describe(self.h, sp, cc, int(n_rows), C.byref(out))
+        if st:
+            _raise(st)
+        return {name: getattr(out, name) for name, _ in L.DescribeStats._fields_}
+
+    def quantiles(self, col, n_rows, percentiles):
+        """percentile(sorted non-null values, p) (stats/descriptive.rs:169-200) for 1 to 16 values of p in [0, 100], in any
+        order, on the device (pandrs_hip_quantiles).  `col` as in describe.  -> (float64 numpy array, one value per p,
+        NaN when the column has no non-null cell; the non-null count)."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        ps = np.ascontiguousarray(percentiles, dtype=np.float64).reshape(-1)
+        out = np.empty(max(ps.shape[0], 1), np.float64)
+        cnt = C.c_int64(0)
+        st = self.lib.pandrs_hip_quantiles(self.h, sp, cc, int(n_rows), ps.ctypes.data_as(C.POINTER(C.c_double)), int(ps.shape[0]),
+                                           out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt))
+        if st:
+            _raise(st)
+        return out[:ps.shape[0]], cnt.value

@@ -314,6 +314,20 @@ def get_context():
     return _default_ctx
 
 
+# StatDescribe's keys in stats_list order (stats.rs:74-83) and the pandrs_hip_describe_stats field behind each
+_DESCRIBE_FIELDS = (("count", "count"), ("mean", "mean"), ("std", "std"), ("min", "min"), ("25%", "q1"), ("50%", "median"),
+                    ("75%", "q3"), ("max", "max"))
+
+
+class StatDescribe:                   # src/optimized/split_dataframe/stats.rs:13-19
+    def __init__(self, stats_list):
+        self.stats_list = list(stats_list)        # ordered (name, value) pairs
+        self.stats = dict(self.stats_list)
+
+    def __repr__(self):
+        return "StatDescribe(%r)" % (self.stats_list,)
+
+
 _WINDOW_OPS = {"sum": L.WINDOW_SUM, "mean": L.WINDOW_MEAN, "var": L.WINDOW_VAR, "std": L.WINDOW_STD, "min": L.WINDOW_MIN,
                "max": L.WINDOW_MAX, "count": L.WINDOW_COUNT}
 _ROLLING_OPS = set(_WINDOW_OPS.values())
@@ -614,6 +628,37 @@ class OptimizedDataFrame:
         if st["count"] == 0:                       # aggregate.rs:135, :148
             raise EmptyError(L.ERR_OPERATION_FAILED, "Column '%s' is empty" % name)
         return float(st["max"])
+
+    # -- describe (split_dataframe/stats.rs:50-171 over stats/descriptive.rs:91-200) ---------------------------
+    def describe(self, column_name):
+        """OptimizedDataFrame::describe (stats.rs:50-151): count, mean, std (two passes, count - 1), min, the 25 / 50 / 75
+        percentiles (linear interpolation at (p / 100) * (count - 1)) and max of the non-null cells of an Int64
+        (`v as f64`) or Float64 column, from one device call (pandrs_hip_describe: a radix select, no sort).  ->
+        StatDescribe.  Errors before any device call: ColumnNotFound, ColumnTypeMismatch for Error::Type (a String or
+        Boolean column, as sum()).  InvalidValue for a column without a non-null cell (descriptive.rs:92-96) and for one
+        with a single non-null cell (the reference's confidence interval refuses 0 degrees of freedom,
+        stats/distributions.rs:188-193).  NaN cells order after every number (pandrs_hip.h)."""
+        col = self.column(column_name)
+        if col.dtype not in (L.I64, L.F64):        # Error::Type (stats.rs:146-149)
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a numeric type" % column_name)
+        st = get_context().describe(col.view(), col.len()) if col.len() else {"count": 0}
+        if st["count"] == 0:
+            raise InvalidValue("Cannot compute statistics for empty data")
+        if st["count"] == 1:
+            raise InvalidValue("Degrees of freedom must be positive")
+        return StatDescribe([(key, float(st[field])) for key, field in _DESCRIBE_FIELDS])
+
+    def describe_all(self):
+        """OptimizedDataFrame::describe_all (stats.rs:157-171): {column name -> StatDescribe} of every Int64 / Float64
+        column; a column whose describe fails (no non-null cell) is left out."""
+        results = {}
+        for name in self.column_names:
+            if self.column(name).dtype in (L.I64, L.F64):
+                try:
+                    results[name] = self.describe(name)
+                except InvalidValue:                # stats.rs:164: `if let Ok(desc)`; a device failure is still raised
+                    pass
+        return results
 
     # -- joins (join.rs:32-73) -----------------------------------------------------------------------------
     def inner_join(self, other, left_on, right_on):
