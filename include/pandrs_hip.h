@@ -653,6 +653,51 @@ int32_t pandrs_hip_describe(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs
 int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                              const double *percentiles, int32_t n_percentiles, double *out, int64_t *out_count);
 
+/* ---- rank of one numeric column ---------------------------------------------------------------------------------------------
+ * PandasCompatExt::rank(column, RankMethod) (src/dataframe/pandas_compat/functions.rs:193-236, RankMethod at
+ * pandas_compat/types.rs:48-59, known answer functions.rs:4393-4404): out[i], i in [0, n_rows), = the rank of row i, ascending
+ * and 1-based.  The m rankable cells are taken in ascending STABLE order (the reference's sort_by is stable); a tie run
+ * occupies the 0-based positions [s, e):
+ *   AVERAGE  (s + e + 1) / 2.0          MIN  s + 1          MAX  e
+ *   FIRST    position + 1: ties rank in original row order          DENSE  the 1-based number of the run.
+ * Ties are the reference's `==` (:202): for F64 numeric equality, so -0.0 ties 0.0, as in pandrs_hip_sort_indices.  Every
+ * result is an integer or half-integer below 2^33 built from integers: bit for bit the reference's, whatever the memory space.
+ * col is I64 or F64, with or without a null mask; any other dtype: PANDRS_HIP_ERR_TYPE_MISMATCH.
+ * How (rank.hip): pandrs_hip_sort_indices' stable radix sort leaves the permutation on the device (NaN after every number,
+ * nulls after NaN); one pass over sorted positions marks where a tie run starts (the cell differs from its predecessor's; the
+ * cells themselves are compared) as one bit per position, with every tile's number of starts and its first and last one; one
+ * small workgroup carries the open run and the start count in from the tiles to the left and the next start in from the right
+ * (two levels, every hand-off a kernel boundary); a last pass turns each position into its run's start, end and dense number
+ * and writes out[perm[p]].  FIRST needs no boundaries, DENSE no run ends.
+ * Geometry (tests read it): rank_tile_rows = 2048 sorted positions per workgroup iteration, rank_blocks_per_cu = 4, grid =
+ * min(rank_blocks_per_cu x compute units, ceil(n_rows / rank_tile_rows)) workgroups striding over the tiles.
+ * Deviations:
+ *  - NaN and null: the reference never terminates on a NaN cell (at :202 the inner `while` does not advance because NaN ==
+ *    NaN is false, and `i = j` repeats) and returns Err(InvalidValue) on a missing value (src/dataframe/base.rs:555-561).
+ *    Here a NaN cell and a null cell get rank NaN and take no rank (pandas' na_option="keep"); the m rankable cells are
+ *    ranked 1 .. m.
+ *  - I64: the reference casts to f64 (base.rs:569), which ties neighbours beyond 2^53 and leaves their FIRST order to row
+ *    order.  Here I64 cells are compared as integers, exactly: the position pandrs_hip_describe takes for I64 order statistics.
+ * Host columns are staged; device and resident columns are read in place (data and out 8-byte aligned; a null mask at any
+ * byte offset, bits past n_rows ignored); out (n_rows doubles) lives in out_mem_space.  pandrs_hip_get_timings' n_partitions
+ * is the number of radix passes, as for the sort (0 when every cell is equal); the rank phase is PANDRS_HIP_PHASE_AGGREGATE.
+ * Workspace, sized up front: pandrs_hip_sort_indices' for one key (24 bytes per row, plus 8 per row for a code beyond 64 bits: a
+ * full-range I64 column with a null has a 65-bit code) plus, for the rank phase, 8 bytes per row (the permutation) and 1 / 8
+ * byte per row plus 24 bytes per rank_tile_rows rows (start bits and tile summaries): 32.2 bytes per row for a code of up to
+ * 64 bits; staging: the host column and a host out.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
+ * col / out, a method outside 0 .. 4 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written.
+ * Out of scope: a descending order, pct, a grouped rank, nlargest / nsmallest, rank through the legacy string frame, and
+ * OptimizedDataFrame::mann_whitney_u (split_dataframe/stats.rs:332: its ties are a chained |a - b| < EPSILON, not equality, and
+ * its p-value is an approximation of the reference's own). */
+typedef enum pandrs_hip_rank_method {   /* RankMethod, types.rs:48-59, same order */
+    PANDRS_HIP_RANK_AVERAGE = 0, PANDRS_HIP_RANK_MIN = 1, PANDRS_HIP_RANK_MAX = 2,
+    PANDRS_HIP_RANK_FIRST = 3, PANDRS_HIP_RANK_DENSE = 4
+} pandrs_hip_rank_method;
+
+int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                        int32_t method, int32_t out_mem_space, double *out);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

@@ -9,6 +9,7 @@
 //                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167;
 //                             rolling / expanding / ewm: src/dataframe/window.rs:13-160 (series/window.rs)
 //                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
+//                             rank: src/dataframe/pandas_compat/functions.rs:193-236
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -224,6 +225,9 @@ inline std::string key_string(int32_t dtype, uint64_t cell, bool is_null, const 
 }
 }  // namespace detail
 
+// RankMethod (src/dataframe/pandas_compat/types.rs:48-59), same order: the values of pandrs_hip_rank_method
+enum class RankMethod : int32_t { Average = 0, Min = 1, Max = 2, First = 3, Dense = 4 };
+
 // StatDescribe (src/optimized/split_dataframe/stats.rs:13-19): count, mean, std, min, 25%, 50%, 75%, max
 struct StatDescribe {
     std::unordered_map<std::string, double> stats;
@@ -327,6 +331,22 @@ public:
                         {"25%", st.q1}, {"50%", st.median}, {"75%", st.q3}, {"max", st.max}};                  // stats.rs:74-83
         for (auto &kv : d.stats_list) d.stats[kv.first] = kv.second;
         return d;
+    }
+    // rank (PandasCompatExt::rank, src/dataframe/pandas_compat/functions.rs:193-236): the ascending 1-based rank of every row
+    // of an Int64 or Float64 column from one pandrs_hip_rank call (the stable radix sort, tie-run boundaries, a scatter); a
+    // tie run at sorted positions [s, e) ranks (s + e + 1) / 2 (Average), s + 1 (Min), e (Max), position + 1 in row order
+    // (First) or the run's number (Dense).  Errors before any device call: ColumnNotFound, Type (a String or Boolean column).
+    // A NaN or null cell gets NaN and takes no rank; Int64 cells are compared as integers (pandrs_hip.h).
+    std::vector<double> rank(const std::string &column_name, RankMethod method = RankMethod::Average) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        std::vector<double> ranks(row_count_);
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_rank(detail::context(), mem_space(), &v, (int64_t)row_count_, (int32_t)method,
+                                          PANDRS_HIP_MEM_HOST, ranks.data()));
+        }
+        return ranks;
     }
     // describe_all (stats.rs:157-171): every Int64 / Float64 column; one whose describe fails with InvalidValue is left out
     std::map<std::string, StatDescribe> describe_all() const {

@@ -497,6 +497,13 @@ int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
     return pandrs::describe_entry(ctx, mem_space, col, n_rows, percentiles, n_percentiles, out, out_count, nullptr);
 } catch (...) { return pandrs::on_exception("pandrs_hip_quantiles"); }
 
+int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                        int32_t method, int32_t out_mem_space, double *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "rank: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::rank_entry(ctx, mem_space, col, n_rows, method, out_mem_space, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_rank"); }
+
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {
     if (!out_sum || !out_sum_sq || !out_count) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce_moments: bad arguments");

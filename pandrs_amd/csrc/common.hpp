@@ -378,6 +378,9 @@ int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_colu
 // describe.hip: out_stats != nullptr = describe (25 / 50 / 75 and the moments), else the caller's percentiles
 int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *percentiles,
                        int32_t n_percentiles, double *out_q, int64_t *out_count, pandrs_hip_describe_stats *out_stats);
+// rank.hip: the ascending 1-based rank of every row (method = pandrs_hip_rank_method), NaN for NaN and null cells
+int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method,
+                   int32_t out_mem_space, double *out);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

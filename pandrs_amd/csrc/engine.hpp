@@ -192,6 +192,13 @@ inline int32_t nested_status(pandrs_hip_ctx *c, int32_t st, int32_t not_taken) {
 size_t two_pass_workspace_bytes(int64_t n_rows, int n_cols8, int n_cols1);
 size_t engine_workspace_bytes(int64_t n_rows, int n_cols8, int n_cols1);
 
+// sort.hip: the stable order of n_rows (> 0) rows by `keys` (device-readable; d_rank = the string pool's rank table for U32CODE
+// keys), left on the device.  The caller holds c->mu, has begun the timings and staged host columns.  d_out != nullptr: the
+// int64 permutation is written there.  d_out == nullptr: *perm_out = n_rows int64 taken from c->work, which is sized for the
+// sort, the permutation and extra_work more bytes; the caller takes its own buffers from c->work after the call.
+int32_t sort_order_device(pandrs_hip_ctx *c, const KeyDesc *keys, int32_t n_keys, const int32_t *ascending, const uint32_t *d_rank,
+                          int64_t n_codes, int64_t n_rows, int64_t *d_out, size_t extra_work, int64_t **perm_out);
+
 // segsort.hip: sorts every partition [0, n_parts) of (keys, payload) ascending by (key, payload),
 // in place, whatever the partition sizes.  `enc`: 0 = payload compared as is, 1 = f64 bits and
 // 2 = i64 rewritten to their order-preserving u64 encodings (and left encoded).

@@ -293,49 +293,19 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(SortPass p) 
 // ------------------------------------------------------------------------------------------------------------------
 struct SortDigit { uint32_t word, shift, dbits; };
 
-int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
-                           const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
-                           int32_t out_mem_space, int64_t *out_idx) {
-    if (!c || !keys || n_keys <= 0 || n_rows < 0 || n_codes < 0 || (n_rows > 0 && !out_idx))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: bad arguments");
-    ST_TRY(check_mem_space("sort_indices", mem_space, out_mem_space));
-    if (n_rows >= (int64_t(1) << 32))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: %lld rows; one call takes fewer than 2^32", (long long)n_rows);
-    bool any_string = false;
-    for (int k = 0; k < n_keys; k++) {
-        const int dt = keys[k].dtype;
-        if (dt < PANDRS_HIP_I64 || dt > PANDRS_HIP_BOOLBITS)
-            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: key %d has dtype %d (CELL64 is not a frame column type)", k, dt);
-        if (dt == PANDRS_HIP_U32CODE && (!code_rank || n_codes == 0))
-            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: string key %d needs the string-pool rank table (code_rank)", k);
-        if (n_rows > 0 && !keys[k].data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: key %d has no data", k);
-        any_string |= dt == PANDRS_HIP_U32CODE;
-    }
-    if (n_rows == 0) return 0;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    timings_begin(c);
+// The stable order of n_rows (> 0) rows by keys the device can read, left on the device; the caller holds c->mu, has begun
+// the timings and staged what was on the host.  d_out != nullptr: the permutation is written there (pandrs_hip_sort_indices).
+// d_out == nullptr: *perm_out = n_rows int64 taken from c->work, which is then sized for the sort plus extra_work bytes: the
+// caller takes its own buffers from c->work after the call (rank.hip).
+int32_t sort_order_device(pandrs_hip_ctx *c, const KeyDesc *keys, int32_t n_keys, const int32_t *ascending, const uint32_t *d_rank,
+                          int64_t n_codes, int64_t n_rows, int64_t *d_out, size_t extra_work, int64_t **perm_out) {
     const size_t n = (size_t)n_rows;
-
-    // ---- host columns (and the rank table with them) are staged; device columns are read in place ----
+    const size_t own_work = (d_out ? 0 : Arena::padded(n * 8)) + extra_work;   // 0 for pandrs_hip_sort_indices
     std::vector<SortKeyDesc> kd(n_keys);
-    int64_t *d_out = nullptr;
-    Stager stg{c, mem_space, out_mem_space};
-    {
-        PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        const size_t rank_bytes = any_string ? (size_t)n_codes * 4 : 0;
-        size_t need = stg.in_size(code_rank, rank_bytes) + stg.out_size(out_idx, n * 8);
-        for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
-        ST_TRY(stg.reserve(need));
-        const void *d_rank = stg.in(code_rank, rank_bytes);
-        for (int k = 0; k < n_keys; k++) {
-            const ColView v = stg.col(keys[k], n_rows);
-            kd[k].key = KeyDesc{v.data, v.mask, nullptr, keys[k].dtype};
-            kd[k].rank = keys[k].dtype == PANDRS_HIP_U32CODE ? (const uint32_t *)d_rank : nullptr;
-            kd[k].n_codes = (uint64_t)n_codes;
-        }
-        d_out = stg.out(out_idx, n * 8);
-        if (stg.status) return stg.status;
+    for (int k = 0; k < n_keys; k++) {
+        kd[k].key = keys[k];
+        kd[k].rank = keys[k].dtype == PANDRS_HIP_U32CODE ? d_rank : nullptr;
+        kd[k].n_codes = (uint64_t)n_codes;
     }
 
     // ---- code widths: one min / max pass per key, one read-back for all ----
@@ -379,6 +349,10 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
     }
     const uint32_t W = (total_bits + 63) / 64;
     if (W == 0) {                                           // every key constant: the identity permutation
+        if (own_work) {
+            ST_TRY(c->work.ensure(own_work + 4096, c->stream));
+            if (!d_out && !(d_out = c->work.take<int64_t>(n))) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (sort)");
+        }
         PhaseTimer pt(c, PANDRS_HIP_PHASE_SCATTER);
         hipLaunchKernelGGL(sort_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n_rows, d_out);
         HIP_TRY(hipGetLastError());
@@ -392,7 +366,8 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
         const size_t S = (n + 31) & ~size_t(31);            // word stride in rows (whole 256-byte pieces)
         ST_TRY(c->work.ensure(Arena::padded((size_t)W * S * 8) + Arena::padded(n * 8) + 2 * Arena::padded(n * 4) +
                               2 * Arena::padded(n_counts * 4 + 4) + Arena::padded(scan_seg_count(n_counts) * 4) +
-                              Arena::padded((size_t)W * 16) + 4096, c->stream));
+                              Arena::padded((size_t)W * 16) + 4096 + own_work, c->stream));
+        if (!d_out && !(d_out = c->work.take<int64_t>(n))) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (sort)");
         uint64_t *words = c->work.take<uint64_t>((size_t)W * S);
         uint64_t *kbuf = c->work.take<uint64_t>(n);
         uint32_t *rA = c->work.take<uint32_t>(n), *rB = c->work.take<uint32_t>(n);
@@ -500,6 +475,54 @@ int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hi
         c->timings.algorithmic_bytes = alg;
         c->timings.n_partitions = (int64_t)plan.size();
     }
+    if (perm_out) *perm_out = d_out;
+    return 0;
+}
+
+int32_t sort_indices_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys,
+                           const int32_t *ascending, const uint32_t *code_rank, int64_t n_codes, int64_t n_rows,
+                           int32_t out_mem_space, int64_t *out_idx) {
+    if (!c || !keys || n_keys <= 0 || n_rows < 0 || n_codes < 0 || (n_rows > 0 && !out_idx))
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: bad arguments");
+    ST_TRY(check_mem_space("sort_indices", mem_space, out_mem_space));
+    if (n_rows >= (int64_t(1) << 32))
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: %lld rows; one call takes fewer than 2^32", (long long)n_rows);
+    bool any_string = false;
+    for (int k = 0; k < n_keys; k++) {
+        const int dt = keys[k].dtype;
+        if (dt < PANDRS_HIP_I64 || dt > PANDRS_HIP_BOOLBITS)
+            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: key %d has dtype %d (CELL64 is not a frame column type)", k, dt);
+        if (dt == PANDRS_HIP_U32CODE && (!code_rank || n_codes == 0))
+            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: string key %d needs the string-pool rank table (code_rank)", k);
+        if (n_rows > 0 && !keys[k].data) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "sort_indices: key %d has no data", k);
+        any_string |= dt == PANDRS_HIP_U32CODE;
+    }
+    if (n_rows == 0) return 0;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    timings_begin(c);
+    const size_t n = (size_t)n_rows;
+
+    // ---- host columns (and the rank table with them) are staged; device columns are read in place ----
+    std::vector<KeyDesc> kd(n_keys);
+    const uint32_t *d_rank = nullptr;
+    int64_t *d_out = nullptr;
+    Stager stg{c, mem_space, out_mem_space};
+    {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
+        const size_t rank_bytes = any_string ? (size_t)n_codes * 4 : 0;
+        size_t need = stg.in_size(code_rank, rank_bytes) + stg.out_size(out_idx, n * 8);
+        for (int k = 0; k < n_keys; k++) need += stg.col_size(keys[k], n_rows);
+        ST_TRY(stg.reserve(need));
+        d_rank = (const uint32_t *)stg.in(code_rank, rank_bytes);
+        for (int k = 0; k < n_keys; k++) {
+            const ColView v = stg.col(keys[k], n_rows);
+            kd[k] = KeyDesc{v.data, v.mask, nullptr, keys[k].dtype};
+        }
+        d_out = stg.out(out_idx, n * 8);
+        if (stg.status) return stg.status;
+    }
+    ST_TRY(sort_order_device(c, kd.data(), n_keys, ascending, d_rank, n_codes, n_rows, d_out, 0, nullptr));
     ST_TRY(stg.copy_back(n * 8));
     ST_TRY(timings_end(c));
     HIP_TRY(hipStreamSynchronize(c->stream));

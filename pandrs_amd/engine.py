@@ -797,3 +797,38 @@ class Context:
         if st:
             _raise(st)
         return out[:ps.shape[0]], cnt.value
+
+    # -- rank (radix sort, tie-run boundaries, scatter) ------------------------------------------------------------
+    def rank(self, col, n_rows, method, out=None, out_device=None):
+        """The ascending 1-based rank of every row of one I64 / F64 column on the device (pandrs_hip_rank;
+        PandasCompatExt::rank, src/dataframe/pandas_compat/functions.rs:193-236).  `col` is a (data, mask, dtype) triple on
+        the host or the device, or a ResidentColumn; method is L.RANK_AVERAGE / MIN / MAX / FIRST / DENSE.  NaN and null
+        cells get NaN and take no rank.  `out`: a float64 numpy array or torch CUDA tensor of at least n_rows elements to
+        write into.  -> n_rows float64 ranks: `out` when given; else a torch tensor on this context's device for device /
+        resident columns (or out_device=True), else a numpy array."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n = int(n_rows)
+        if out is not None:
+            out_device = _is_torch(out)
+            if out_device:
+                import torch
+                ok = out.dtype == torch.float64 and out.is_contiguous() and out.is_cuda and out.numel() >= n
+            else:
+                ok = isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.size >= n
+            if not ok:
+                raise ValueError("out must be a contiguous float64 numpy array or CUDA tensor of at least n_rows elements")
+            if out_device:
+                self._wait_for_producer()
+        else:
+            if out_device is None:
+                out_device = sp == L.MEM_DEVICE
+            if out_device:
+                import torch
+                out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
+            else:
+                out = np.empty(n, np.float64)
+        st = self.lib.pandrs_hip_rank(self.h, sp, cc, n, int(method), L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if n else None)
+        if st:
+            _raise(st)
+        return out[:n]

@@ -48,6 +48,14 @@ class AggregateOp(IntEnum):          # types.rs:11-34, same order
     Nunique = 11                     # not in the reference's enum: the legacy AggFunc::Nunique (src/dataframe/groupby.rs:41)
 
 
+class RankMethod(IntEnum):           # pandas_compat/types.rs:48-59, same order
+    Average = 0
+    Min = 1
+    Max = 2
+    First = 3
+    Dense = 4
+
+
 class JoinType(IntEnum):             # join.rs:11-20
     Inner = 0
     Left = 1
@@ -659,6 +667,23 @@ class OptimizedDataFrame:
                 except InvalidValue:                # stats.rs:164: `if let Ok(desc)`; a device failure is still raised
                     pass
         return results
+
+    # -- rank (dataframe/pandas_compat/functions.rs:193-236) ----------------------------------------------------
+    def rank(self, column_name, method=RankMethod.Average):
+        """PandasCompatExt::rank (functions.rs:193-236): the ascending 1-based rank of every row of an Int64 or Float64
+        column, from one device call (pandrs_hip_rank: the stable radix sort, tie-run boundaries, a scatter).  A tie run
+        at sorted positions [s, e) ranks (s + e + 1) / 2 (Average), s + 1 (Min), e (Max), position + 1 in row order
+        (First) or the run's number (Dense).  -> float64 numpy array of row_count() ranks (the reference's Vec<f64>).
+        Errors before any device call: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column (as describe).
+        Deviations (pandrs_hip.h): a NaN or null cell gets NaN and takes no rank (the reference loops forever on NaN and
+        returns InvalidValue on a missing value); Int64 cells are compared as integers, not as f64."""
+        col = self.column(column_name)
+        if col.dtype not in (L.I64, L.F64):
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a numeric type" % column_name)
+        method = RankMethod(method)
+        if col.len() == 0:
+            return np.empty(0, np.float64)
+        return np.asarray(get_context().rank(col.view(), col.len(), int(method), out_device=False), dtype=np.float64)
 
     # -- joins (join.rs:32-73) -----------------------------------------------------------------------------
     def inner_join(self, other, left_on, right_on):
