@@ -36,7 +36,7 @@ __global__ __launch_bounds__(AG_THREADS) void aggregate2_kernel(AggArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t T = a.T, T1 = T + (SMALL ? 3 : 2), tid = threadIdx.x;   // slot T: the key equal to the table sentinel; T + 1: the NULL key (SMALL)
     // LDS: keys[T1] | states[round_states][T1] | gsz[T1] (u32) | ctrl[T] (u8) | misc[40] | queue[16][QCAP]   (T multiple of 16)
-    // state order (fixed by run_engine for this kernel): adds of source 0..n-1, then per source its
+    // state order (fixed by LeanLayout, groupby.hip, for this kernel): adds of source 0..n-1, then per source its
     // min-type states (min, ~max), then the non-null counts
     uint64_t *keys = reinterpret_cast<uint64_t *>(smem);
     uint64_t *st = keys + T1;

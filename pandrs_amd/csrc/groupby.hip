@@ -787,6 +787,20 @@ static int32_t append_groups(pandrs_hip_ctx *c, GroupbyResult &res, size_t cap, 
     return 0;
 }
 
+// The result's arrays for `cap` groups from its arena: keys [n_keys][cap] (row 0 holds the engine's cell), their null flags, and
+// `out_cols` columns of partial states or of aggregates.
+static int32_t take_result(pandrs_hip_ctx *c, Arena &rarena, GroupbyResult &res, size_t cap, int n_keys_out, bool partials, size_t out_cols) {
+    out_cols = std::max<size_t>(out_cols, 1);
+    ST_TRY(rarena.ensure((size_t)n_keys_out * (Arena::padded(cap * 8) + Arena::padded(cap)) + out_cols * Arena::padded(cap * 8 + 256) + 8192, c->stream));
+    res.cap = (int64_t)cap;
+    res.keys = rarena.take<uint64_t>(cap * n_keys_out);
+    res.key_null = rarena.take<uint8_t>(cap * n_keys_out);
+    if (partials) res.states = rarena.take<uint64_t>(cap * out_cols + 32);
+    else res.aggs = rarena.take<double>(cap * out_cols + 32);
+    if (!res.keys || !res.key_null || (!res.states && !res.aggs)) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "result arena too small");
+    return 0;
+}
+
 struct EngSrc;
 static int32_t run_two_level(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge, bool partials,
                              int n_aggs, int key_dtype, int n_keys_out, int res_slot, int64_t est, int64_t groups_per_run);
@@ -802,11 +816,58 @@ struct EngSrc {
     int n_states() const { return (st_add >= 0) + (st_min >= 0) + (st_max >= 0) + (st_nn >= 0) + (st_fadd >= 0) + (st_ssq >= 0); }
 };
 
-int64_t lean_table_slots(const pandrs_hip_ctx *c, int round_states) {
-    const size_t slot_bytes = 13 + 8 * (size_t)round_states;
-    int64_t T = (int64_t)(((size_t)c->lds_bytes - 512 - 192 - AGG2_LDS_EXTRA) / slot_bytes) - 3;
-    return std::min<int64_t>(T, 32768) & ~int64_t(15);
+// Profile of one source = the kernel instantiation it needs: kind << 4 | ops (1 sum, 2 min, 4 max) << 1 | validity.
+// valid_bytes count as validity.  The paths that read the ORIGINAL columns (small, absorb, clustered, direct) know null bitmaps only:
+// each of them refuses valid_bytes sources before it compares profiles, so there the bit says null_bits alone.
+static int src_profile(const EngSrc &e) {
+    const int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
+    return (e.kind << 4) | (ops << 1) | ((e.null_bits || e.valid_bytes) ? 1 : 0);
 }
+// the profile every source has; -1 when they differ or there is no source
+static int uniform_profile(const std::vector<EngSrc> &srcs) {
+    const int profile = srcs.empty() ? -1 : src_profile(srcs[0]);
+    for (auto &e : srcs) if (src_profile(e) != profile) return -1;
+    return profile;
+}
+
+// The lean kernels' fixed LDS state order inside one round of `n_src` sources of one `profile` (aggregate2.hip, absorb.hip's spill side,
+// clustered.hip): the adds of source 0..n-1, then per source its min-type states (min, max), then the non-null counts of the sources
+// that have one, in source order.  The kernels compute the same indices from (profile, n_src); this is the host's one statement of it.
+struct LeanLayout {
+    LeanLayout(int profile, int n_src) : mm(((profile >> 2) & 1) + ((profile >> 3) & 1)), mbase(((profile >> 1) & 1) ? n_src : 0), next_nn(mbase + n_src * mm) {}
+    int add(int s) const { return s; }
+    int min(int s) const { return mbase + s * mm; }
+    int max(int s) const { return mbase + s * mm + mm - 1; }
+    int nn() { return next_nn++; }          // (the sources in order, once per source that has a count)
+    // source `s` of the round: the LDS ids of its states into sd and st_lds[absolute id], their round where the caller keeps one
+    void place(const EngSrc &e, int s, SrcDev &sd, int8_t *st_lds, int8_t *st_round = nullptr, int round = 0) {
+        auto put = [&](int8_t abs_id, int8_t &lds_id, int at) {
+            if (abs_id < 0) return;
+            if (st_round) st_round[abs_id] = (int8_t)round;
+            st_lds[abs_id] = (int8_t)at; lds_id = (int8_t)at;
+        };
+        put(e.st_add, sd.st_add, add(s)); put(e.st_min, sd.st_min, min(s)); put(e.st_max, sd.st_max, max(s));
+        if (e.st_nn >= 0) put(e.st_nn, sd.st_nn, nn());
+    }
+    int mm, mbase, next_nn;
+};
+// The older kernel's order (and its direct mode's): a round's states as they come, source by source, from `next` on.
+static void place_in_turn(const EngSrc &e, int round, int &next, SrcDev &sd, int8_t *st_round, int8_t *st_lds) {
+    auto place = [&](int8_t abs_id, int8_t &lds_id) {
+        if (abs_id < 0) return;
+        st_round[abs_id] = (int8_t)round; st_lds[abs_id] = (int8_t)next; lds_id = (int8_t)next; next++;
+    };
+    place(e.st_add, sd.st_add); place(e.st_min, sd.st_min); place(e.st_max, sd.st_max); place(e.st_nn, sd.st_nn);
+    place(e.st_fadd, sd.st_fadd); place(e.st_ssq, sd.st_ssq);
+}
+
+// LDS table slots for `round_states` 8-byte states per group: the lean kernels' (13-byte slots: u32 group sizes, one tag byte, no position
+// map; 16-slot groups) and the older kernel's, its direct mode included (20-byte slots, 4-key buckets)
+static int64_t table_slots(const pandrs_hip_ctx *c, size_t slot_bytes, size_t extra, int64_t multiple) {
+    return std::min<int64_t>((int64_t)(((size_t)c->lds_bytes - 512 - 192 - extra) / slot_bytes) - 3, 32768) & ~(multiple - 1);
+}
+int64_t lean_table_slots(const pandrs_hip_ctx *c, int round_states) { return table_slots(c, 13 + 8 * (size_t)round_states, AGG2_LDS_EXTRA, 16); }
+static int64_t older_table_slots(const pandrs_hip_ctx *c, int round_states) { return table_slots(c, 20 + 8 * (size_t)round_states, 0, 4); }
 
 constexpr int32_t SMALL_NOT_TAKEN = -1000;
 constexpr int64_t SMALL_MAX_ROWS = int64_t(1) << 21;
@@ -825,14 +886,10 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     if (c->opt.no_small || N > SMALL_MAX_ROWS || n_src < 1 || !pl.mergeable || pl.needs_second_pass || c->opt.generic_aggregate ||
         c->opt.agg_v1 || c->opt.deterministic)
         return SMALL_NOT_TAKEN;
-    auto prof_of = [](const EngSrc &e) {
-        int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
-        return (e.kind << 4) | (ops << 1) | (e.null_bits ? 1 : 0);
-    };
-    const int profile = prof_of(srcs[0]);
+    const int profile = uniform_profile(srcs);
     int round_states = 0;
     for (auto &e : srcs) {
-        if (e.rowidx || e.valid_bytes || !e.data || prof_of(e) != profile) return SMALL_NOT_TAKEN;
+        if (e.rowidx || e.valid_bytes || !e.data || profile < 0) return SMALL_NOT_TAKEN;
         round_states += e.n_states();
     }
     if (!aggregate2_small_has(n_src, profile) || round_states > SMALL_MAX_STATES) return SMALL_NOT_TAKEN;
@@ -851,37 +908,20 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     uint32_t *counters = g_cnt + GS;
 
     const size_t slot_bytes = 13 + 8 * (size_t)round_states;
-    int64_t T = (int64_t)(((size_t)c->lds_bytes - 512 - 192 - AGG2_LDS_EXTRA) / slot_bytes) - 3;
-    T = std::min<int64_t>(T, 32768) & ~int64_t(15);
+    const int64_t T = lean_table_slots(c, round_states);
     if (T < 64) return SMALL_NOT_TAKEN;
 
     const size_t cap = (size_t)std::min<int64_t>(N, (int64_t)GS);
-    ST_TRY(rarena.ensure((size_t)n_keys_out * (Arena::padded(cap * 8) + Arena::padded(cap)) +
-                         std::max<size_t>(n_aggs, 1) * Arena::padded(cap * 8 + 256) + 8192, c->stream));
-    res.cap = (int64_t)cap;
-    res.keys = rarena.take<uint64_t>(cap * n_keys_out);
-    res.key_null = rarena.take<uint8_t>(cap * n_keys_out);
-    res.aggs = rarena.take<double>(cap * std::max<size_t>(n_aggs, 1) + 32);
-    if (!res.keys || !res.key_null || !res.aggs) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "result arena too small");
+    ST_TRY(take_result(c, rarena, res, cap, n_keys_out, /*partials=*/false, (size_t)n_aggs));
 
     AggArgs aa{};
     int8_t st_lds[MAX_STATES];
     for (int k = 0; k < MAX_STATES; k++) st_lds[k] = -1;
-    const int mm = ((profile >> 2) & 1) + ((profile >> 3) & 1);
-    const int mbase = ((profile >> 1) & 1) ? n_src : 0;
-    int next_nn = mbase + n_src * mm;
+    LeanLayout lay(profile, n_src);
     for (int s = 0; s < n_src; s++) {
         const EngSrc &e = srcs[s];
-        SrcDev &sd = aa.src[s];
-        sd = SrcDev{static_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};     // SMALL: valid = the column's null bitmap
-        auto put = [&](int8_t abs_id, int8_t &lds_id, int at) {
-            if (abs_id < 0) return;
-            st_lds[abs_id] = (int8_t)at; lds_id = (int8_t)at;
-        };
-        put(e.st_add, sd.st_add, s);
-        put(e.st_min, sd.st_min, mbase + s * mm);
-        put(e.st_max, sd.st_max, mbase + s * mm + mm - 1);
-        if (e.st_nn >= 0) put(e.st_nn, sd.st_nn, next_nn++);
+        aa.src[s] = SrcDev{static_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};     // SMALL: valid = the column's null bitmap
+        lay.place(e, s, aa.src[s], st_lds);
     }
     aa.dkey = rs.key; aa.s_rows = (uint32_t)N;
     // rows per workgroup: every workgroup flushes its groups with global atomics, so more than ~64 of them cost more in
@@ -938,7 +978,6 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     return 0;
 }
 
-// Core: groups rs by key and reduces the plan's states.  Result retained in c->gb.
 // ---- hot-key absorb-and-spill (kernels: absorb.hip) ------------------------------------------------------------------
 // One pass over the ORIGINAL columns folds the rows of the keys that found a slot in a workgroup's LDS table; the other
 // rows are spilled straight into P_s radix partitions (per-workgroup regions), the lean aggregate folds those regions
@@ -1020,9 +1059,7 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
     a.sp_keys = c->absorb.take<uint64_t>(region_rows + 16);
     AggArgs aa{};
     int next = 0;
-    // the lean aggregate's fixed LDS state order (run_engine): adds of source 0..n-1, per source its min-type states, then the counts
-    const int v2_mm = ((profile >> 2) & 1) + ((profile >> 3) & 1), v2_mbase = ((profile >> 1) & 1) ? n_src : 0;
-    int v2_next_nn = v2_mbase + n_src * v2_mm;
+    LeanLayout lay(profile, n_src);             // (the spill side's tables)
     for (int k = 0; k < MAX_STATES; k++) { aa.st_round[k] = -1; aa.st_lds[k] = -1; }
     for (int s = 0; s < n_src; s++) {
         const EngSrc &e = srcs[s];
@@ -1037,16 +1074,8 @@ static int32_t run_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl
             lds_id = (int8_t)next; a.lds_abs[next] = abs_id; a.lds_kind[next] = pl.kinds[abs_id]; next++;
         };
         place(e.st_add, a.st_add[s]); place(e.st_min, a.st_min[s]); place(e.st_max, a.st_max[s]); place(e.st_nn, a.st_nn[s]);
-        SrcDev &sd = aa.src[s];
-        sd = SrcDev{a.sp_vals[s], a.sp_valid[s], e.kind, -1, -1, -1, -1, -1, -1, {0}};
-        auto put = [&](int8_t abs_id, int8_t &lds_id, int at) {
-            if (abs_id < 0) return;
-            aa.st_round[abs_id] = 0; aa.st_lds[abs_id] = (int8_t)at; lds_id = (int8_t)at;
-        };
-        put(e.st_add, sd.st_add, s);
-        put(e.st_min, sd.st_min, v2_mbase + s * v2_mm);
-        put(e.st_max, sd.st_max, v2_mbase + s * v2_mm + v2_mm - 1);
-        if (e.st_nn >= 0) put(e.st_nn, sd.st_nn, v2_next_nn++);
+        aa.src[s] = SrcDev{a.sp_vals[s], a.sp_valid[s], e.kind, -1, -1, -1, -1, -1, -1, {0}};
+        lay.place(e, s, aa.src[s], aa.st_lds, aa.st_round);
     }
     if (!a.sp_keys) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "absorb arena too small");
     a.n_lds_states = next;
@@ -1184,14 +1213,10 @@ static int32_t run_clustered(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     const int64_t N = rs.n_rows;
     const int n_src = (int)srcs.size();
     if (n_src < 1 || n_src > 4 || N >= (int64_t(1) << 32) - (int64_t(1) << 22)) return CLUSTERED_NOT_TAKEN;
-    auto prof_of = [](const EngSrc &e) {
-        int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
-        return (e.kind << 4) | (ops << 1) | (e.null_bits ? 1 : 0);
-    };
-    const int profile = prof_of(srcs[0]);
+    const int profile = uniform_profile(srcs);
     int round_states = 0;
     for (auto &e : srcs) {
-        if (e.rowidx || e.valid_bytes || !e.data || e.st_fadd >= 0 || e.st_ssq >= 0 || prof_of(e) != profile) return CLUSTERED_NOT_TAKEN;
+        if (e.rowidx || e.valid_bytes || !e.data || e.st_fadd >= 0 || e.st_ssq >= 0 || profile < 0) return CLUSTERED_NOT_TAKEN;
         round_states += e.n_states();
     }
     if (!clustered_has(n_src, profile)) return CLUSTERED_NOT_TAKEN;
@@ -1227,21 +1252,11 @@ static int32_t run_clustered(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     HIP_TRY(hipMemsetAsync(counters, 0, 256, c->stream));
     AggArgs aa{};
     for (int k = 0; k < MAX_STATES; k++) { aa.st_round[k] = -1; aa.st_lds[k] = -1; }
-    // the lean aggregate's fixed LDS state order: adds of source 0..n-1, per source its min-type states, then the counts
-    const int mm = ((profile >> 2) & 1) + ((profile >> 3) & 1), mbase = ((profile >> 1) & 1) ? n_src : 0;
-    int next_nn = mbase + n_src * mm;
+    LeanLayout lay(profile, n_src);
     for (int s = 0; s < n_src; s++) {
         const EngSrc &e = srcs[s];
-        SrcDev &sd = aa.src[s];
-        sd = SrcDev{static_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};     // SMALL: valid = the column's null bitmap
-        auto put = [&](int8_t abs_id, int8_t &lds_id, int at) {
-            if (abs_id < 0) return;
-            aa.st_round[abs_id] = 0; aa.st_lds[abs_id] = (int8_t)at; lds_id = (int8_t)at;
-        };
-        put(e.st_add, sd.st_add, s);
-        put(e.st_min, sd.st_min, mbase + s * mm);
-        put(e.st_max, sd.st_max, mbase + s * mm + mm - 1);
-        if (e.st_nn >= 0) put(e.st_nn, sd.st_nn, next_nn++);
+        aa.src[s] = SrcDev{static_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};     // SMALL: valid = the column's null bitmap
+        lay.place(e, s, aa.src[s], aa.st_lds, aa.st_round);
     }
     aa.dkey = rs.key; aa.s_rows = (uint32_t)N; aa.s_chunk = (uint32_t)chunk;
     {
@@ -1280,21 +1295,38 @@ static int32_t run_clustered(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
     return nested_status(c, st, CLUSTERED_NOT_TAKEN);
 }
 
-int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge,
-                          bool partials, int n_aggs, int key_dtype, int n_keys_out, int res_slot) {
-    if (res_slot < 0 || res_slot > 2) return fail(PANDRS_HIP_ERR_COMPUTATION, "engine nesting too deep");
-    if (c->test_throw_nested && c->quiet > 0) { c->test_throw_nested = false; throw std::bad_alloc(); }     // tests: what a host allocation below could do
-    GroupbyResult &res = res_slot == 0 ? c->gb : (res_slot == 1 ? c->gb2 : c->gb3);
-    Arena &rarena = res_slot == 0 ? c->result : (res_slot == 1 ? c->result2 : c->result3);
-    res = GroupbyResult{};
-    res.n_keys = n_keys_out; res.n_aggs = n_aggs; res.n_state = 1 + pl.n_states; res.partials = partials;
-    res.key_dtype = key_dtype;
-    const int64_t N = rs.n_rows;
-    if (N == 0) { res.valid = true; return 0; }
-    if (N >= (int64_t(1) << 32) - SC_TILE_MAX)
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "n_rows %lld exceeds the 2^32 per-call limit", (long long)N);
+// ---- run_engine's stages in the order it goes through them: build_sources, (run_small), estimate_and_decide_absorb, (run_absorb, run_clustered),
+// run_direct, plan_rounds, then per attempt lay_out_and_partition, launch_attempt, finish_attempt.  EngCall: what the call was asked.
+struct EngCall {
+    const RowSource &rs; const Plan &pl;
+    bool merge, partials; int n_aggs, key_dtype, n_keys_out, res_slot;
+    int64_t est; int n_src;         // the estimate of the groups; engine sources
+    GroupbyResult &res; Arena &rarena;
+};
+// What plan_rounds decides.  The attempt loop changes P alone.
+struct EnginePlan {
+    int n_rounds = 1, round_states = 0, max_spr = 0;     // round r takes sources [round_begin[r], round_begin[r + 1]) with round_prof[r]'s instantiation
+    int8_t round_begin[MAX_ROUNDS + 1];
+    int round_prof[MAX_ROUNDS], uni_profile = -1;
+    bool use_v2 = false, v2_ok = false, two_level = false;     // two_level: more groups than one radix level holds, go to run_two_level
+    int64_t T = 0, P = 0, auto_slice_rows = 0, P_LIMIT = 0, groups_per_run = 0;     // groups_per_run: of a two-level sub-run
+    size_t slot_bytes = 0;
+    uint32_t seed = 0;              // of the partition's and the tables' hash
+};
+// One attempt: what its three stages hand on.
+struct Attempt {
+    int index = 0;                  // in: the attempt's number
+    bool exact = false;             // in: an earlier capacity-mode run overflowed a region, take the exact histogram
+    bool sampled = false, polled = false;
+    AggArgs aa{};
+    PartInfo part;
+    size_t cap = 0, side_cap = 0;   // groups the result / the side buffers hold
+    uint32_t ov_cap = 0;            // rows the overflow buffer holds (0: there is none)
+};
+constexpr int32_t DIRECT_NOT_TAKEN = -1003, ATTEMPT_FAILED = -1004;
 
-    // ---- engine sources.  merge mode: every partial state column is its own single-op source.
+// ---- engine sources.  merge mode: every partial state column is its own single-op source; raw rows: the plan's sources + the row index.
+static std::vector<EngSrc> build_sources(const RowSource &rs, const Plan &pl, bool merge) {
     std::vector<EngSrc> srcs;
     if (merge) {
         for (int s = 0; s < pl.n_states; s++) {
@@ -1310,220 +1342,164 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
             }
             srcs.push_back(e);
         }
-    } else {
-        for (int s = 0; s < pl.n_src; s++) {
-            EngSrc e;
-            e.data = rs.val_data[s]; e.null_bits = rs.val_null_bits[s]; e.valid_bytes = rs.val_valid_bytes[s]; e.kind = pl.src_kind[s];
-            e.st_add = pl.st_add[s]; e.st_min = pl.st_min[s]; e.st_max = pl.st_max[s]; e.st_nn = pl.st_nn[s];
-            e.st_fadd = pl.st_fadd[s]; e.st_ssq = pl.st_ssq[s];
-            srcs.push_back(e);
-        }
-        if (pl.st_firstrow >= 0) {
-            EngSrc e;
-            e.kind = 1; e.rowidx = true; e.st_min = pl.st_firstrow; e.st_max = pl.st_lastrow;
-            e.data = rs.row_index;             // nullptr: the row's own index
-            srcs.push_back(e);
-        }
+        return srcs;
     }
-    // (Inside one call, for the row slices of an oversized partition, these merge after all.  First / Last: min / max of the row
-    // index merge like any other state and the value is looked up behind the merge — across shards a row index means nothing.
-    // Std / Var: every slice runs the two passes over its own rows, the merge adds the between-slice term — aggregate.hpp, MergeVar.)
-    const bool nested_slice_merge = merge && !partials && c->quiet > 0;
-    if ((partials || merge) && !pl.mergeable && !nested_slice_merge)
-        return fail(PANDRS_HIP_ERR_OPERATION_FAILED,
-                    "Std/Var/Median/First/Last partial states are not mergeable across shards yet");
+    for (int s = 0; s < pl.n_src; s++) {
+        EngSrc e;
+        e.data = rs.val_data[s]; e.null_bits = rs.val_null_bits[s]; e.valid_bytes = rs.val_valid_bytes[s]; e.kind = pl.src_kind[s];
+        e.st_add = pl.st_add[s]; e.st_min = pl.st_min[s]; e.st_max = pl.st_max[s]; e.st_nn = pl.st_nn[s];
+        e.st_fadd = pl.st_fadd[s]; e.st_ssq = pl.st_ssq[s];
+        srcs.push_back(e);
+    }
+    if (pl.st_firstrow >= 0) {
+        EngSrc e;
+        e.kind = 1; e.rowidx = true; e.st_min = pl.st_firstrow; e.st_max = pl.st_lastrow;
+        e.data = rs.row_index;             // nullptr: the row's own index
+        srcs.push_back(e);
+    }
+    return srcs;
+}
+
+// ---- the estimate (unless the caller brought one: `est` > 0) and the absorb decision.
+// hot-key absorb-and-spill (absorb.hip) is decided from the estimate's own sample: its key table is kept for one
+// more look (how many rows do the most frequent keys hold?) when the call could take that path at all
+struct AbsorbDecision { int profile = -1; int64_t T = 0; bool take = false; const uint64_t *hot_image = nullptr; };
+static int32_t estimate_and_decide_absorb(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const std::vector<EngSrc> &srcs, bool merge,
+                                          int res_slot, int64_t &est, AbsorbDecision &ad) {
+    const int64_t N = rs.n_rows;
     const int n_src = (int)srcs.size();
-    // (merges of more than 16 states: the record loop of aggregate_kernel<.., MERGE> walks the states at run time; the catch-all instantiation a
-    // Std / Var merge needs keeps register arrays for 16 sources)
-    if (n_src > (merge ? MAX_MERGE_SRC : MAX_SRC) || (merge && n_src > MAX_SRC && pl.needs_second_pass))
-        return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "too many states to merge (%d)", n_src);
-
-    // ---- small calls (launch-bound: the reference's 1 M-row case): two launches, no estimate, no partition
-    if (!merge && !partials && res_slot == 0 && !c->quiet && c->opt.groups_hint <= 0 && !rs.pre) {
-        int32_t st = run_small(c, rs, pl, srcs, n_aggs, n_keys_out, res, rarena);
-        if (st != SMALL_NOT_TAKEN) return st;
+    bool ok = !merge && !rs.pre && pl.mergeable && c->opt.no_absorb <= 0 && res_slot == 0 && !c->quiet &&
+              N >= (int64_t(1) << (c->opt.no_absorb < 0 ? 16 : 22)) &&      // (no_absorb = -1, tests / fuzz: small inputs too)
+              n_src >= 1 && n_src <= MAX_ABS_SRC && c->opt.partitions <= 0 && !c->opt.generic_aggregate && !c->opt.deterministic;
+    for (auto &e : srcs) ok = ok && !e.valid_bytes && !e.rowidx && e.st_fadd < 0 && e.st_ssq < 0;
+    if (ok) {
+        ad.profile = uniform_profile(srcs);
+        if (ad.profile >= 0 && (!absorb_has(n_src, ad.profile) || !aggregate2_has(n_src, ad.profile))) ad.profile = -1;
     }
-
-    // ---- workspace upper bound so that one ensure() covers the whole call (incl. retries)
-    // the capacity layout of radix_partition_sampled over-allocates the partitioned columns by <= 25 %
-    size_t ws = rs.pre ? engine_workspace_bytes(0, 0, 0) + (size_t(64) << 20)            // the partitioned columns are the producer's
-                       : engine_workspace_bytes(N + N / 4 + 131072, 1 + n_src + (merge ? 1 : 0), n_src);
-    ST_TRY(c->work.ensure(ws, c->stream));
-    int64_t est = rs.pre ? std::max<int64_t>(rs.pre->est_groups, 1) : c->opt.groups_hint;
-    // hot-key absorb-and-spill (absorb.hip) is decided from the estimate's own sample: its key table is kept for one
-    // more look (how many rows do the most frequent keys hold?) when the call could take that path at all
-    int absorb_profile = -1;
-    {
-        auto prof_of = [](const EngSrc &e) {
-            int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
-            return (e.kind << 4) | (ops << 1) | (e.null_bits ? 1 : 0);
-        };
-        bool ok = !merge && !rs.pre && pl.mergeable && c->opt.no_absorb <= 0 && res_slot == 0 && !c->quiet &&
-                  N >= (int64_t(1) << (c->opt.no_absorb < 0 ? 16 : 22)) &&      // (no_absorb = -1, tests / fuzz: small inputs too)
-                  n_src >= 1 && n_src <= MAX_ABS_SRC && c->opt.partitions <= 0 && !c->opt.generic_aggregate && !c->opt.deterministic;
-        for (auto &e : srcs) ok = ok && !e.valid_bytes && !e.rowidx && e.st_fadd < 0 && e.st_ssq < 0;
-        if (ok) {
-            absorb_profile = prof_of(srcs[0]);
-            for (int s = 1; s < n_src; s++) if (prof_of(srcs[s]) != absorb_profile) absorb_profile = -1;
-            if (absorb_profile >= 0 && (!absorb_has(n_src, absorb_profile) || !aggregate2_has(n_src, absorb_profile))) absorb_profile = -1;
-        }
-    }
-    if (est <= 0) ST_TRY(estimate_groups(c, rs.key, N, &est, /*keep_table=*/absorb_profile >= 0));
+    if (est <= 0) ST_TRY(estimate_groups(c, rs.key, N, &est, /*keep_table=*/ad.profile >= 0));
     else { c->clustered_rows = false; c->clumped_rows = false; c->est_near_same = 0.0; c->est_far_same = 0.0; c->est_far_equal = 0; }          // no sample taken: nothing known about the row order
     c->timings.estimated_groups = est;
-    int64_t T_abs = 0;
-    bool do_absorb = false;
-    const uint64_t *hot_image = nullptr;
-    if (c->est_kept) {
-        int lds_states = 0;
-        for (auto &e : srcs) lds_states += (e.st_add >= 0) + (e.st_min >= 0) + (e.st_max >= 0) + (e.st_nn >= 0);
-        T_abs = absorb_table_slots(c, lds_states);
-        int total_states = 0;
-        for (auto &e : srcs) total_states += e.n_states();
-        const int64_t Td = std::min<int64_t>((int64_t)(((size_t)c->lds_bytes - 512 - 192) / (20 + 8 * (size_t)total_states)) - 3, 32768) & ~int64_t(3);
-        const bool direct_would = Td >= 64 && est * 2 <= Td && !c->opt.no_direct && (N >= (int64_t(1) << 22) || c->opt.no_direct < 0);
-        if (T_abs >= 256 && !c->clustered_rows && !c->opt.no_direct && est * 2 <= T_abs) {
-            // every group fits a workgroup's table with room to spare: the absorb pass IS the few-groups direct path (nothing spills),
-            // with the leaner kernel (100 M rows, 1 K groups: 0.59 -> 0.45 ms for one sum, 0.89 -> 0.70 for six aggregates)
-            estimate_release(c);
-            do_absorb = true;
-        } else if (T_abs >= 256 && !c->clustered_rows && !direct_would && (est <= 64 * T_abs || (c->est_repeat_share >= 0.5 && res_slot == 0)) &&
-                   N >= (int64_t(1) << (c->opt.no_absorb < 0 ? 16 : 24))) {
-            // not where the direct path answers, not where the table is a drop in the ocean — unless the sample itself shows a hot set
-            // (half its rows on keys sighted three times or more: a long tail behind hot keys, compact spill): absorb when the most
-            // frequent keys — as many as the table takes — hold most of the rows
-            double share = 0.0;
-            // (the same bar behind a long tail — the compact spill.  0.65 kept 95 % of C2's rows on 2 K keys, of which the table holds 1.2 K, on the
-            // radix path (4.6 instead of 5.4 ms) but sent a join's pair groupby with 60 % of the pairs in 16 groups + 4 M singleton groups there too: 20 ms instead of 4.9)
-            const double min_share = c->opt.no_absorb < 0 ? 0.0 : 0.60;
-            ST_TRY(estimate_coverage(c, rs.key, N, (int64_t)((double)T_abs * 0.80), &share, c->opt.no_hot_image ? 0 : T_abs, ABSORB_SEED, min_share, &hot_image));
-            do_absorb = share >= min_share;        // (no_absorb = -1, tests: whenever it is possible)
-        } else estimate_release(c);
-    }
-    if (do_absorb) {
-        const int32_t st = run_absorb(c, rs, pl, srcs, absorb_profile, T_abs, est, partials, n_aggs, key_dtype, n_keys_out, res_slot, hot_image);
-        if (st != ABSORB_NOT_TAKEN) return st;
-    }
-    if (c->clustered_rows && !merge && !rs.pre && pl.mergeable && !pl.needs_second_pass && res_slot == 0 && !c->quiet && !c->opt.no_clustered &&
-        !c->opt.generic_aggregate && !c->opt.agg_v1 && !c->opt.deterministic && c->opt.partitions <= 0 && N >= (int64_t(1) << 20)) {
-        const int32_t st = run_clustered(c, rs, pl, srcs, est, partials, n_aggs, key_dtype, n_keys_out, res_slot);
-        if (st != CLUSTERED_NOT_TAKEN) return st;
-    }
+    if (!c->est_kept) return 0;
+    int lds_states = 0, total_states = 0;
+    for (auto &e : srcs) { lds_states += (e.st_add >= 0) + (e.st_min >= 0) + (e.st_max >= 0) + (e.st_nn >= 0); total_states += e.n_states(); }
+    ad.T = absorb_table_slots(c, lds_states);
+    const int64_t Td = older_table_slots(c, total_states);          // (what run_direct will find)
+    const bool direct_would = Td >= 64 && est * 2 <= Td && !c->opt.no_direct && (N >= (int64_t(1) << 22) || c->opt.no_direct < 0);
+    if (ad.T >= 256 && !c->clustered_rows && !c->opt.no_direct && est * 2 <= ad.T) {
+        // every group fits a workgroup's table with room to spare: the absorb pass IS the few-groups direct path (nothing spills),
+        // with the leaner kernel (100 M rows, 1 K groups: 0.59 -> 0.45 ms for one sum, 0.89 -> 0.70 for six aggregates)
+        estimate_release(c);
+        ad.take = true;
+    } else if (ad.T >= 256 && !c->clustered_rows && !direct_would && (est <= 64 * ad.T || (c->est_repeat_share >= 0.5 && res_slot == 0)) &&
+               N >= (int64_t(1) << (c->opt.no_absorb < 0 ? 16 : 24))) {
+        // not where the direct path answers, not where the table is a drop in the ocean — unless the sample itself shows a hot set
+        // (half its rows on keys sighted three times or more: a long tail behind hot keys, compact spill): absorb when the most
+        // frequent keys — as many as the table takes — hold most of the rows
+        double share = 0.0;
+        // (the same bar behind a long tail — the compact spill.  0.65 kept 95 % of C2's rows on 2 K keys, of which the table holds 1.2 K, on the
+        // radix path (4.6 instead of 5.4 ms) but sent a join's pair groupby with 60 % of the pairs in 16 groups + 4 M singleton groups there too: 20 ms instead of 4.9)
+        const double min_share = c->opt.no_absorb < 0 ? 0.0 : 0.60;
+        ST_TRY(estimate_coverage(c, rs.key, N, (int64_t)((double)ad.T * 0.80), &share, c->opt.no_hot_image ? 0 : ad.T, ABSORB_SEED, min_share, &ad.hot_image));
+        ad.take = share >= min_share;        // (no_absorb = -1, tests: whenever it is possible)
+    } else estimate_release(c);
+    return 0;
+}
 
-    // ---- low-cardinality direct path: when every group fits one LDS table with room to spare,
-    // skip the radix partition altogether.  Each workgroup pre-aggregates a contiguous row range
-    // of the ORIGINAL columns (one HBM pass), emits its groups as partial records, and the few
-    // records (<= tasks x G) are merged by the normal engine.  Also the cure for one-hot-key
-    // inputs (bool keys, a dominant key), where a radix partition would put all rows on one CU.
-    // (below a few million rows the whole call is launch-bound and the two-stage direct path loses)
+// ---- low-cardinality direct path: when every group fits one LDS table with room to spare,
+// skip the radix partition altogether.  Each workgroup pre-aggregates a contiguous row range
+// of the ORIGINAL columns (one HBM pass), emits its groups as partial records, and the few
+// records (<= tasks x G) are merged by the normal engine.  Also the cure for one-hot-key
+// inputs (bool keys, a dominant key), where a radix partition would put all rows on one CU.
+// (below a few million rows the whole call is launch-bound and the two-stage direct path loses)
+// DIRECT_NOT_TAKEN: the call does not qualify, or a task overflowed its table or its record budget: the partitioned path answers.
+static int32_t run_direct(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const std::vector<EngSrc> &srcs, int64_t est, bool merge,
+                          bool partials, int n_aggs, int key_dtype, int n_keys_out, int res_slot) {
+    const int64_t N = rs.n_rows;
+    const int n_src = (int)srcs.size();
     bool has_valid_bytes = false;
     for (auto &e : srcs) has_valid_bytes |= e.valid_bytes != nullptr;
     // (pl.n_states <= MAX_MERGE_SRC: the records' merge takes every state as a source of its own — 8 columns x sum / min / max = 24 states
     // used to FAIL the call here, "too many states to merge", when a merge took 16)
-    if (!merge && !rs.pre && pl.mergeable && !c->opt.no_direct && !has_valid_bytes && n_src <= MAX_SRC && pl.n_states <= MAX_MERGE_SRC &&
-        (N >= (int64_t(1) << 22) || c->opt.no_direct < 0)) {
-        int total_states = 0;
-        for (auto &e : srcs) total_states += e.n_states();
-        const size_t sb = 20 + 8 * (size_t)total_states;
-        int64_t Td = (int64_t)(((size_t)c->lds_bytes - 512 - 192) / sb) - 3;
-        Td = std::min<int64_t>(Td, 32768) & ~int64_t(3);
-        if (Td >= 64 && est * 2 <= Td) {
-            const uint32_t n_tasks = (uint32_t)std::min<int64_t>(std::max<int64_t>(N / 65536, 1), 1024);
-            const uint32_t chunk = (uint32_t)((N + n_tasks - 1) / n_tasks);
-            const size_t dcap = (size_t)n_tasks * (size_t)std::min<int64_t>(Td + 2, std::max<int64_t>(est * 4, 64) + 2);
-            const size_t n_state = 1 + (size_t)pl.n_states;
-            ST_TRY(c->temp.ensure(Arena::padded(dcap * 8) + Arena::padded(dcap) + n_state * Arena::padded(dcap * 8 + 256) + 8192, c->stream));
-            uint64_t *rk = c->temp.take<uint64_t>(dcap);
-            uint8_t *rn = c->temp.take<uint8_t>(dcap);
-            uint64_t *rst = c->temp.take<uint64_t>(dcap * n_state + 32);
-            uint32_t *counters = c->temp.take<uint32_t>(64);
-            if (!rk || !rn || !rst || !counters) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "temp arena too small");
-            HIP_TRY(hipMemsetAsync(counters, 0, 256, c->stream));
-            AggArgs aa{};
-            aa.direct = 1; aa.dkey = rs.key; aa.d_rows = (uint32_t)N; aa.d_chunk = chunk; aa.launch_grid = n_tasks;
-            aa.T = (uint32_t)Td; aa.seed = 0x9E3779B9u; aa.n_src = n_src; aa.n_states = pl.n_states;
-            aa.n_fin = 0; aa.partials = 1; aa.n_rounds = 1; aa.round_states = total_states; aa.second_pass = 0;
-            aa.round_src_begin[0] = 0; aa.round_src_begin[1] = (int8_t)n_src;
-            std::memcpy(aa.kinds, pl.kinds, sizeof aa.kinds);
-            int next = 0;
-            for (int k = 0; k < MAX_STATES; k++) { aa.st_round[k] = -1; aa.st_lds[k] = -1; }
-            for (int sidx = 0; sidx < n_src; sidx++) {
-                EngSrc &e = srcs[sidx];
-                SrcDev &sd = aa.src[sidx];
-                sd = SrcDev{reinterpret_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};
-                auto place = [&](int8_t abs_id, int8_t &lds_id) {
-                    if (abs_id < 0) return;
-                    aa.st_round[abs_id] = 0; aa.st_lds[abs_id] = (int8_t)next; lds_id = (int8_t)next; next++;
-                };
-                place(e.st_add, sd.st_add); place(e.st_min, sd.st_min); place(e.st_max, sd.st_max); place(e.st_nn, sd.st_nn);
-            }
-            // capacity per task is bounded by dcap / n_tasks records: a task that finds more groups than that
-            // (the estimate was too low) must not write past the buffer -> it raises the overflow flag instead
-            aa.out_keys = rk; aa.out_null = rn; aa.out_states = rst; aa.cap = dcap; aa.counters = counters;
-            aa.d_task_cap = (uint32_t)(dcap / n_tasks);
-            int profile = -1;
-            if (n_src > 0 && !c->opt.generic_aggregate) {
-                auto prof_of = [](const EngSrc &e) {
-                    int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
-                    return (e.kind << 4) | (ops << 1) | (e.null_bits ? 1 : 0);
-                };
-                profile = prof_of(srcs[0]);
-                for (int sidx = 1; sidx < n_src; sidx++) if (prof_of(srcs[sidx]) != profile) profile = -1;
-            }
-            {
-                PhaseTimer pt(c, PANDRS_HIP_PHASE_AGGREGATE);
-                launch_aggregate(c, aa, n_src, profile, (size_t)(Td + 3) * sb + 192);
-                HIP_TRY(hipGetLastError());
-            }
-            uint32_t *h = reinterpret_cast<uint32_t *>(c->pinned);
-            HIP_TRY(hipMemcpyAsync(h, counters, 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (h[1] == 0) {
-                c->timings.n_partitions = 0; c->timings.table_slots = Td;
-                // (the merge input is tiny and its cardinality is known)
-                const int32_t st = merge_records(c, record_source(rk, rn, rst, dcap, h[0]), est, 0, pl, partials, n_aggs, key_dtype,
-                                                 n_keys_out, res_slot);
-                c->timings.estimated_groups = est;
-                return st;
-            }
-            // a task overflowed its table or its record budget: fall through to the partitioned path
-        }
+    if (merge || rs.pre || !pl.mergeable || c->opt.no_direct || has_valid_bytes || n_src > MAX_SRC || pl.n_states > MAX_MERGE_SRC ||
+        !(N >= (int64_t(1) << 22) || c->opt.no_direct < 0))
+        return DIRECT_NOT_TAKEN;
+    int total_states = 0;
+    for (auto &e : srcs) total_states += e.n_states();
+    const int64_t Td = older_table_slots(c, total_states);
+    if (!(Td >= 64 && est * 2 <= Td)) return DIRECT_NOT_TAKEN;
+    const uint32_t n_tasks = (uint32_t)std::min<int64_t>(std::max<int64_t>(N / 65536, 1), 1024);
+    const uint32_t chunk = (uint32_t)((N + n_tasks - 1) / n_tasks);
+    const size_t dcap = (size_t)n_tasks * (size_t)std::min<int64_t>(Td + 2, std::max<int64_t>(est * 4, 64) + 2);
+    const size_t n_state = 1 + (size_t)pl.n_states;
+    ST_TRY(c->temp.ensure(Arena::padded(dcap * 8) + Arena::padded(dcap) + n_state * Arena::padded(dcap * 8 + 256) + 8192, c->stream));
+    uint64_t *rk = c->temp.take<uint64_t>(dcap);
+    uint8_t *rn = c->temp.take<uint8_t>(dcap);
+    uint64_t *rst = c->temp.take<uint64_t>(dcap * n_state + 32);
+    uint32_t *counters = c->temp.take<uint32_t>(64);
+    if (!rk || !rn || !rst || !counters) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "temp arena too small");
+    HIP_TRY(hipMemsetAsync(counters, 0, 256, c->stream));
+    AggArgs aa{};
+    aa.direct = 1; aa.dkey = rs.key; aa.d_rows = (uint32_t)N; aa.d_chunk = chunk; aa.launch_grid = n_tasks;
+    aa.T = (uint32_t)Td; aa.seed = 0x9E3779B9u; aa.n_src = n_src; aa.n_states = pl.n_states;
+    aa.n_fin = 0; aa.partials = 1; aa.n_rounds = 1; aa.round_states = total_states; aa.second_pass = 0;
+    aa.round_src_begin[0] = 0; aa.round_src_begin[1] = (int8_t)n_src;
+    std::memcpy(aa.kinds, pl.kinds, sizeof aa.kinds);
+    int next = 0;
+    for (int k = 0; k < MAX_STATES; k++) { aa.st_round[k] = -1; aa.st_lds[k] = -1; }
+    for (int s = 0; s < n_src; s++) {
+        const EngSrc &e = srcs[s];
+        aa.src[s] = SrcDev{reinterpret_cast<const uint64_t *>(e.data), e.null_bits, e.kind, -1, -1, -1, -1, -1, -1, {0}};
+        place_in_turn(e, 0, next, aa.src[s], aa.st_round, aa.st_lds);
     }
+    // capacity per task is bounded by dcap / n_tasks records: a task that finds more groups than that
+    // (the estimate was too low) must not write past the buffer -> it raises the overflow flag instead
+    aa.out_keys = rk; aa.out_null = rn; aa.out_states = rst; aa.cap = dcap; aa.counters = counters;
+    aa.d_task_cap = (uint32_t)(dcap / n_tasks);
+    const int profile = c->opt.generic_aggregate ? -1 : uniform_profile(srcs);
+    {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_AGGREGATE);
+        launch_aggregate(c, aa, n_src, profile, (size_t)(Td + 3) * (20 + 8 * (size_t)total_states) + 192);
+        HIP_TRY(hipGetLastError());
+    }
+    uint32_t *h = reinterpret_cast<uint32_t *>(c->pinned);
+    HIP_TRY(hipMemcpyAsync(h, counters, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h[1]) return DIRECT_NOT_TAKEN;
+    c->timings.n_partitions = 0; c->timings.table_slots = Td;
+    // (the merge input is tiny and its cardinality is known)
+    const int32_t st = merge_records(c, record_source(rk, rn, rst, dcap, h[0]), est, 0, pl, partials, n_aggs, key_dtype, n_keys_out, res_slot);
+    c->timings.estimated_groups = est;
+    return st;
+}
 
-    // ---- rounds x table geometry x fan-out.  Fewer sources per round => fewer bytes per slot =>
-    // more slots per LDS table => fewer radix partitions (cheaper scatter), at the price of
-    // re-reading the partition's keys once per extra round.
-    const size_t lds_budget = (size_t)c->lds_bytes - 512;
+// ---- rounds x table geometry x fan-out.  Fewer sources per round => fewer bytes per slot =>
+// more slots per LDS table => fewer radix partitions (cheaper scatter), at the price of
+// re-reading the partition's keys once per extra round.
+// `srcs` is not const: rounds grouped by profile stable-sort the sources by profile, and every later stage sees that order.
+static int32_t plan_rounds(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, std::vector<EngSrc> &srcs, int64_t est, bool merge,
+                           bool partials, int res_slot, EnginePlan &ep) {
+    const int64_t N = rs.n_rows;
+    const int n_src = (int)srcs.size();
     const double LOAD = c->opt.load_pct > 0 ? c->opt.load_pct / 100.0 : 0.70;
     int spr = n_src > 0 ? n_src : 1;           // sources per round
-    int n_rounds = 1, round_states = 0, max_spr = 0;
-    int64_t T = 0, P = 0, auto_slice_rows = 0;
-    int8_t round_begin[MAX_ROUNDS + 1];
+    int &n_rounds = ep.n_rounds, &round_states = ep.round_states, &max_spr = ep.max_spr;
+    int64_t &T = ep.T, &P = ep.P;
     // uniform profile: raw rows, every source the same kind / ops / validity (one kernel instantiation)
-    auto prof_of = [](const EngSrc &e) {
-        int ops = (e.st_add >= 0 ? 1 : 0) | (e.st_min >= 0 ? 2 : 0) | (e.st_max >= 0 ? 4 : 0);
-        return (e.kind << 4) | (ops << 1) | ((e.null_bits || e.valid_bytes) ? 1 : 0);
-    };
-    int uni_profile = -1;
-    if (!merge && n_src > 0 && !c->opt.generic_aggregate && pl.mergeable) {
-        uni_profile = prof_of(srcs[0]);
-        for (int s = 1; s < n_src; s++) if (prof_of(srcs[s]) != uni_profile) uni_profile = -1;
-    }
+    const int uni_profile = ep.uni_profile = (!merge && !c->opt.generic_aggregate && pl.mergeable) ? uniform_profile(srcs) : -1;
     // Columns of MIXED kinds / op sets (f64 and i64 side by side, sums on some and min / max on others): no uniform profile, but the lean
     // kernel's rounds hand on nothing that depends on the profile (keys, tags, output positions) — so the sources are ordered by profile
     // and every round takes up to 4 sources of ONE profile, with that profile's instantiation.  (Before: the older kernel; 4 f64 + 4 i64
     // columns x sum, 50 M rows, 3.8 ms in its rounds of 4, 8-13 ms with a dominant key — experiments/mixed_wide.py, wide_hot.py.)
-    int round_prof[MAX_ROUNDS];
-    for (int r = 0; r < MAX_ROUNDS; r++) round_prof[r] = uni_profile;
+    for (int r = 0; r < MAX_ROUNDS; r++) ep.round_prof[r] = uni_profile;
     bool grouped = false;
     if (uni_profile < 0 && !merge && !rs.pre && !partials && n_src >= 2 && !c->opt.generic_aggregate && pl.mergeable && !pl.needs_second_pass &&
         !c->opt.no_lean_rounds && !c->opt.no_profile_rounds && !c->opt.agg_v1 && c->opt.src_per_round <= 0 && c->opt.partitions <= 0 &&
         (!c->clustered_rows || 1.0 - c->est_near_same > 0.09)) {
         bool all_ok = true;
         for (auto &e : srcs)
-            all_ok = all_ok && !e.rowidx && e.data && e.st_fadd < 0 && e.st_ssq < 0 && !(e.null_bits && e.valid_bytes) && aggregate2_has(1, prof_of(e));
+            all_ok = all_ok && !e.rowidx && e.data && e.st_fadd < 0 && e.st_ssq < 0 && !(e.null_bits && e.valid_bytes) && aggregate2_has(1, src_profile(e));
         if (all_ok) {
-            std::stable_sort(srcs.begin(), srcs.end(), [&](const EngSrc &x, const EngSrc &y) { return prof_of(x) < prof_of(y); });
+            std::stable_sort(srcs.begin(), srcs.end(), [](const EngSrc &x, const EngSrc &y) { return src_profile(x) < src_profile(y); });
             grouped = true;
         }
     }
@@ -1549,14 +1525,14 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
     // (long runs too when there are more than 4 columns: the one-pass path takes at most 4, and the burst kernel in rounds behind the exact
     // partition — sorted rows, 8 columns x 4 aggregates, 50 M rows: 3.3 ms — beats the older kernel's 24 states in one table: 9.6)
     const bool wide_clustered = c->clustered_rows && n_src > 4 && clustered_has(4, uni_profile) && !c->opt.no_burst_kernel;
-    const bool v2_ok = grouped ? lean_rounds_ok
+    const bool v2_ok = ep.v2_ok = grouped ? lean_rounds_ok
                      : (uni_profile >= 0 && !pl.needs_second_pass && (!c->clustered_rows || short_runs || wide_clustered) && !c->opt.agg_v1 &&
                         aggregate2_has(std::min(n_src, 4), uni_profile) && (n_src <= 4 || lean_rounds_ok));
     if (v2_ok && n_src > 4) spr = 4;
     // the older kernel with more than 4 sources in a round is its catch-all instantiation (register arrays for 16 sources: it spills):
     // 4 f64 + 4 i64 columns x sum, 50 M rows, 8.3 ms in one round, 3.8 in two (experiments/mixed_wide.py).  Merges have their own loop.
     if (!v2_ok && !merge && n_src > 4 && !pl.needs_second_pass && rounds_ok) spr = 4;
-    bool use_v2 = false;
+    bool &use_v2 = ep.use_v2;
     // rounds only when one round would need more partitions than this.  The older kernel's rounds are dear (3072); the lean kernel's cost
     // one more pass over the key column per round, which a fan-out beyond ~4 K costs the scatter too (experiments/p_target_sweep.py,
     // C2's 12 states, 100 M rows: 5 M uniform groups one round at P = 5120 5.43 ms, two rounds at 2816 4.82; 7 M: 6.05 / 5.37; 4 M: a tie;
@@ -1566,17 +1542,15 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
         // one round per run of up to 4 sources of one profile
         n_rounds = 0; round_states = 0; max_spr = 0;
         for (int b = 0; b < n_src;) {
-            const int p = prof_of(srcs[b]);
+            const int p = src_profile(srcs[b]);
             int e2 = b, ns = 0;
-            while (e2 < n_src && e2 - b < 4 && prof_of(srcs[e2]) == p) { ns += srcs[e2].n_states(); e2++; }
-            round_begin[n_rounds] = (int8_t)b; round_prof[n_rounds] = p; n_rounds++; round_begin[n_rounds] = (int8_t)e2;
+            while (e2 < n_src && e2 - b < 4 && src_profile(srcs[e2]) == p) { ns += srcs[e2].n_states(); e2++; }
+            ep.round_begin[n_rounds] = (int8_t)b; ep.round_prof[n_rounds] = p; n_rounds++; ep.round_begin[n_rounds] = (int8_t)e2;
             round_states = std::max(round_states, ns); max_spr = std::max(max_spr, e2 - b);
             b = e2;
         }
         use_v2 = true;
-        const size_t sb = 13 + 8 * (size_t)round_states;
-        T = (int64_t)((lds_budget - 192 - AGG2_LDS_EXTRA) / sb) - 3;
-        T = std::min<int64_t>(T, 32768) & ~int64_t(15);
+        T = lean_table_slots(c, round_states);
         P = (int64_t)std::ceil((double)est / ((double)T * (c->opt.load_pct > 0 ? LOAD : 0.6)));
     } else
     for (;; spr = (spr + 1) / 2) {
@@ -1586,27 +1560,26 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
         round_states = 0; max_spr = 0;
         for (int r = 0; r < n_rounds; r++) {
             int b0 = r * spr, b1 = std::min(n_src, b0 + spr), ns = 0;
-            round_begin[r] = (int8_t)b0; round_begin[r + 1] = (int8_t)b1;
+            ep.round_begin[r] = (int8_t)b0; ep.round_begin[r + 1] = (int8_t)b1;
             for (int s = b0; s < b1; s++) ns += srcs[s].n_states();
             round_states = std::max(round_states, ns);
             max_spr = std::max(max_spr, b1 - b0);
         }
-        if (n_src == 0) { round_begin[0] = round_begin[1] = 0; }
+        if (n_src == 0) { ep.round_begin[0] = ep.round_begin[1] = 0; }
         use_v2 = v2_ok && max_spr <= 4 && (n_rounds == 1 || lean_rounds_ok);
-        const size_t slot_bytes = (use_v2 ? 13 : 20) + 8 * (size_t)round_states;    // aggregate2: u32 group sizes, one tag byte, no position map
-        T = (int64_t)((lds_budget - 192 - (use_v2 ? AGG2_LDS_EXTRA : 0)) / slot_bytes) - 3;
-        T = std::min<int64_t>(T, 32768) & (use_v2 ? ~int64_t(15) : ~int64_t(3));   // 16-slot groups / 4-key buckets
+        // aggregate2: u32 group sizes, one tag byte, no position map; 16-slot groups / 4-key buckets
+        T = use_v2 ? lean_table_slots(c, round_states) : older_table_slots(c, round_states);
         // (the lean kernel's rounds have no overflow run behind a full table: planned at load 0.6, an estimate 35 % too low still fits —
         // at 0.7 one that was 25 % too low cost the attempt: 6 M groups estimated as 4.5 M, 10.9 ms against 6.8 for the single round)
         P = (int64_t)std::ceil((double)est / ((double)T * ((use_v2 && n_rounds > 1 && c->opt.load_pct <= 0) ? 0.6 : LOAD)));
         if (c->opt.src_per_round > 0 || spr <= 1 || P <= P_TARGET || pl.needs_second_pass) break;
     }
     if (T < 64) return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "too many aggregate states for one LDS table");
-    const size_t slot_bytes = (use_v2 ? 13 : 20) + 8 * (size_t)round_states;
+    ep.slot_bytes = (use_v2 ? 13 : 20) + 8 * (size_t)round_states;
     if (rs.pre) {
         P = rs.pre->part.P;
         // few large partitions: cut them into ~512 row slices for the chip's workgroups (partial records merged below)
-        if (P < 256) auto_slice_rows = std::max<int64_t>(N / 512, 65536);
+        if (P < 256) ep.auto_slice_rows = std::max<int64_t>(N / 512, 65536);
     } else if (c->opt.partitions > 0) P = c->opt.partitions;
     else {
         // enough workgroups to fill 256 CUs (a partial record carries every state: fewer per workgroup)
@@ -1619,10 +1592,10 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
             N >= (int64_t(1) << 24) && P < p_par && pl.n_states >= 4 && pl.n_states <= MAX_MERGE_SRC) {   // (1-2 states: measured 5 % slower; > 16: the slices' records could not be merged)
             int64_t p_rec = 16;
             while (p_rec * 262144 < p_par * est) p_rec *= 2;
-            if (std::max(P, p_rec) <= 64) { P = std::max(P, p_rec); auto_slice_rows = N / p_par; p_par = 1; }
+            if (std::max(P, p_rec) <= 64) { P = std::max(P, p_rec); ep.auto_slice_rows = N / p_par; p_par = 1; }
         }
         P = std::max<int64_t>(std::max<int64_t>(P, p_par), 1);
-        if (use_v2 && P > c->n_cu && auto_slice_rows == 0) {
+        if (use_v2 && P > c->n_cu && ep.auto_slice_rows == 0) {
             // one persistent workgroup per CU walks P near-equal partitions: a multiple of the CU count has no
             // ragged last round (1152 partitions on 256 CUs = 4.5 rounds, paid as 5).  Round down while the
             // table load stays <= 0.80, else up.
@@ -1630,337 +1603,371 @@ int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool 
             P = (double)est / ((double)down * (double)T) <= 0.80 ? down : up;
         } else if (P > 256) P = (P + 127) / 128 * 128;
     }
-    const int64_t P_LIMIT = c->opt.p_max > 0 ? std::min<int64_t>(c->opt.p_max, P_MAX) : P_MAX;
-    if (rs.pre && (P > P_LIMIT || !v2_ok)) return fail(PANDRS_HIP_ERR_COMPUTATION, "pre-partitioned rows: unsupported plan or fan-out");
-    if (P > P_LIMIT && c->opt.partitions <= 0 && res_slot == 0 && !c->quiet)
-        // more groups than one radix level can hold (P_LIMIT tables of T slots): split by an
-        // independent hash into super-partitions and run the engine on each
-        return run_two_level(c, rs, pl, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot, est,
-                             (int64_t)((double)P_LIMIT * 0.6 * (double)T * LOAD));
-    P = std::min<int64_t>(std::max<int64_t>(P, 1), P_LIMIT);
-
+    ep.P_LIMIT = c->opt.p_max > 0 ? std::min<int64_t>(c->opt.p_max, P_MAX) : P_MAX;
+    if (rs.pre && (P > ep.P_LIMIT || !v2_ok)) return fail(PANDRS_HIP_ERR_COMPUTATION, "pre-partitioned rows: unsupported plan or fan-out");
+    // more groups than one radix level can hold (P_LIMIT tables of T slots): split by an
+    // independent hash into super-partitions and run the engine on each
+    ep.groups_per_run = (int64_t)((double)ep.P_LIMIT * 0.6 * (double)T * LOAD);
+    ep.two_level = P > ep.P_LIMIT && c->opt.partitions <= 0 && res_slot == 0 && !c->quiet;
+    P = std::min<int64_t>(std::max<int64_t>(P, 1), ep.P_LIMIT);
     // (a nested merge — the records of an oversized partition's pieces, of the direct path's chunks — hashes with a seed of its own:
     // the pieces' keys all come from a few of the parent's partitions, i.e. from a few RANGES of the parent's hash, and
     // part_of() maps a range of the same hash onto a handful of the merge's partitions, which then overflow and cost a retry)
-    const uint32_t seed = (merge && res_slot > 0) ? 0x68E31DA5u : 0x9E3779B9u;
+    ep.seed = (merge && res_slot > 0) ? 0x68E31DA5u : 0x9E3779B9u;
+    return 0;
+}
+
+// ---- one attempt, stage 1: the partitioned columns and the LDS place of every state, then the partition itself
+static int32_t lay_out_and_partition(pandrs_hip_ctx *c, const EngCall &k, const EnginePlan &ep, const std::vector<EngSrc> &srcs, Attempt &at) {
+    const RowSource &rs = k.rs; const Plan &pl = k.pl; AggArgs &aa = at.aa;
+    const int64_t N = rs.n_rows, P = ep.P;
+    // capacity mode (no histogram pass): aggregate2 only (it walks a partition's 8 row ranges), unclustered rows
+    at.sampled = rs.pre ? true
+               : ep.use_v2 && !at.exact && !c->clustered_rows && !c->clumped_rows && !c->opt.exact_partition && c->opt.shared_cursors &&
+                 c->opt.scatter_threads != 512 && c->opt.scatter_staged && sampled_partition_ok(N, P);
+    if (rs.pre && (!ep.use_v2 || at.exact || at.index > 0))      // a full table or a dropped run: the producer must start over
+        return fail(PANDRS_HIP_ERR_COMPUTATION, "pre-partitioned rows: a partition did not fit");
+    const size_t NP = rs.pre ? 0 : at.sampled ? (size_t)sampled_partition_rows(N, P) : (size_t)N;     // rows of the partitioned columns
+    uint32_t *counters = c->work.take<uint32_t>(64);
+    uint64_t *pkeys = rs.pre ? const_cast<uint64_t *>(rs.pre->pkeys) : c->work.take<uint64_t>(NP);
+    if (!counters || !pkeys) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
+    HIP_TRY(hipMemsetAsync(counters, 0, 64 * 4, c->stream));
+    aa.counters = counters; aa.pkeys = pkeys;
+
+    ScatterArgs sa{};
+    sa.key = rs.key; sa.pkeys = pkeys; sa.n_rows = N; sa.P = (uint32_t)P; sa.seed = ep.seed;
+    if (k.merge) {
+        int64_t *pgsize = c->work.take<int64_t>(N);
+        if (!pgsize) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
+        sa.mv[sa.n_move++] = MoveDesc{rs.merge_gsize ? (const void *)rs.merge_gsize : (const void *)rs.merge_states, pgsize, 0, 0};
+        aa.pgsize = pgsize;
+    }
+    // LDS index of every state inside its round: LeanLayout for the lean kernel's rounds (each round its own profile), in turn for the older kernel
+    for (int s2 = 0; s2 < MAX_STATES; s2++) { aa.st_round[s2] = -1; aa.st_lds[s2] = -1; }
+    for (int r = 0; r < ep.n_rounds; r++) {
+        int next = 0;
+        LeanLayout lay(ep.round_prof[r], ep.round_begin[r + 1] - ep.round_begin[r]);
+        for (int s = ep.round_begin[r]; s < ep.round_begin[r + 1]; s++) {
+            const EngSrc &e = srcs[s];
+            uint64_t *pv = rs.pre ? const_cast<uint64_t *>(rs.pre->pvals[s]) : c->work.take<uint64_t>(NP);
+            if (!pv) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
+            sa.mv[sa.n_move++] = MoveDesc{e.data, pv, (e.rowidx && !e.data) ? 5 : 0, 0};
+            uint8_t *pvalid = nullptr;
+            if (e.null_bits || e.valid_bytes) {
+                pvalid = c->work.take<uint8_t>(NP);
+                if (!pvalid) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
+                sa.mv[sa.n_move++] = e.null_bits ? MoveDesc{e.null_bits, pvalid, 1, 0} : MoveDesc{e.valid_bytes, pvalid, 2, 0};
+            }
+            aa.src[s] = SrcDev{pv, pvalid, e.kind, -1, -1, -1, -1, -1, -1, {0}};
+            if (ep.use_v2) lay.place(e, s - ep.round_begin[r], aa.src[s], aa.st_lds, aa.st_round, r);
+            else place_in_turn(e, r, next, aa.src[s], aa.st_round, aa.st_lds);
+        }
+    }
+    if (k.merge && pl.needs_second_pass) {
+        if (ep.n_rounds != 1) return fail(PANDRS_HIP_ERR_COMPUTATION, "Std / Var records merge in one round only");
+        for (int s2 = 0; s2 < pl.n_src; s2++) {
+            if (pl.st_ssq[s2] < 0) continue;
+            if (aa.n_mvar >= MAX_MERGE_VAR) return fail(PANDRS_HIP_ERR_COMPUTATION, "too many Std / Var columns to merge");
+            const int8_t ssum = pl.src_kind[s2] == 0 ? pl.st_add[s2] : pl.st_fadd[s2], snn = pl.st_nn[s2];
+            MergeVar &mv = aa.mvar[aa.n_mvar++];
+            mv.ssq = aa.st_lds[pl.st_ssq[s2]]; mv.sum = aa.st_lds[ssum]; mv.nn = snn >= 0 ? aa.st_lds[snn] : (int8_t)-1;
+            mv.sum_col = aa.src[ssum].vals; mv.nn_col = snn >= 0 ? aa.src[snn].vals : nullptr;
+        }
+    }
+    for (int f = 0; f < k.n_aggs && !k.partials; f++) {
+        FinDev &fd = aa.fin[f];
+        fd = FinDev{};
+        fd.op = pl.fin_op[f]; fd.kind = pl.fin_kind[f];
+        fd.st_add = fd.st_nn = fd.st_min = fd.st_max = fd.st_ssq = fd.st_fadd = fd.rowsrc_min = fd.rowsrc_max = -1;
+        int s = pl.fin_src[f];
+        if (s < 0) continue;                                   // COUNT: round 0, group size only
+        auto lds_of = [&](int8_t abs_id) -> int8_t { return abs_id < 0 ? (int8_t)-1 : aa.st_lds[abs_id]; };
+        fd.st_add = lds_of(pl.st_add[s]); fd.st_nn = lds_of(pl.st_nn[s]);
+        fd.st_min = lds_of(pl.st_min[s]); fd.st_max = lds_of(pl.st_max[s]);
+        fd.st_ssq = lds_of(pl.st_ssq[s]); fd.st_fadd = lds_of(pl.st_fadd[s]);
+        int8_t any = pl.st_add[s] >= 0 ? pl.st_add[s] : (pl.st_min[s] >= 0 ? pl.st_min[s] : (pl.st_max[s] >= 0 ? pl.st_max[s] : (pl.st_ssq[s] >= 0 ? pl.st_ssq[s] : (int8_t)-1)));
+        fd.round = any >= 0 ? aa.st_round[any] : 0;
+        if (fd.op == PANDRS_HIP_AGG_FIRST || fd.op == PANDRS_HIP_AGG_LAST) {
+            fd.rowsrc_min = aa.st_lds[pl.st_firstrow]; fd.rowsrc_max = aa.st_lds[pl.st_lastrow];
+            fd.round = aa.st_round[pl.st_firstrow];
+            fd.col_data = rs.fin_data[s] ? rs.fin_data[s] : rs.val_data[s];
+            fd.col_null = rs.fin_data[s] ? rs.fin_null_bits[s] : rs.val_null_bits[s];
+        }
+    }
+    if (rs.pre) at.part = rs.pre->part;
+    else if (at.sampled) ST_TRY(radix_partition_sampled(c, sa, &at.part, PANDRS_HIP_PHASE_HISTOGRAM, PANDRS_HIP_PHASE_SCATTER));
+    else ST_TRY(radix_partition(c, sa, &at.part, PANDRS_HIP_PHASE_HISTOGRAM, PANDRS_HIP_PHASE_SCAN, PANDRS_HIP_PHASE_SCATTER));
+    return 0;
+}
+
+// ---- one attempt, stage 2: the result and the side arenas, the task list, the aggregate's launches; leaves the counters in the pinned
+// words h[0..6]: groups, failed, side records, the scatter's overflow flag, .., rows in the overflow buffer
+static int32_t launch_attempt(pandrs_hip_ctx *c, const EngCall &k, const EnginePlan &ep, Attempt &at) {
+    const RowSource &rs = k.rs; const Plan &pl = k.pl;
+    const bool merge = k.merge, partials = k.partials, use_v2 = ep.use_v2, sampled = at.sampled;
+    const int64_t N = rs.n_rows, P = ep.P, T = ep.T;
+    const int n_rounds = ep.n_rounds, res_slot = k.res_slot, n_src = k.n_src;
+    const uint32_t P1 = (uint32_t)P + 1;
+    GroupbyResult &res = k.res; AggArgs &aa = at.aa; const PartInfo &part = at.part;
+    // oversized partitions (a hot key, heavy skew) are cut into row slices for separate workgroups
+    int n_var_src = 0;
+    for (int s2 = 0; s2 < pl.n_src; s2++) n_var_src += pl.st_ssq[s2] >= 0;
+    const bool slicing = !c->opt.no_slice && (pl.mergeable || (!partials && !merge && n_var_src <= MAX_MERGE_VAR)) && (n_rounds == 1 || (use_v2 && !partials)) && pl.n_states <= MAX_MERGE_SRC;      // (the lean kernel's rounds fill a piece's record round by round)
+    const int64_t slice_rows = c->opt.slice_rows > 0 ? c->opt.slice_rows
+                             : ep.auto_slice_rows > 0 ? ep.auto_slice_rows
+                                                      : std::max<int64_t>(int64_t(1) << 18, (c->opt.wide_slices ? 4 : (c->opt.slice_over > 0 ? c->opt.slice_over : 2)) * (N / std::max<int64_t>(P, 1)));
+    // (cut when far above the average, into pieces of the average size: build_tasks_kernel.  A forced or mid-cardinality
+    // slice length is both at once.)
+    const int64_t piece_rows = (c->opt.slice_rows > 0 || ep.auto_slice_rows > 0 || c->opt.wide_slices) ? slice_rows
+                             : std::min<int64_t>(slice_rows, std::max<int64_t>(int64_t(1) << 16, N / std::max<int64_t>(P, 1)));
+    const int64_t max_slices = slicing ? N / piece_rows + N / slice_rows + 2 : 0;       // slices of multi-slice partitions
+    const size_t side_cap = at.side_cap = (size_t)max_slices * (size_t)(T + 2);
+    // (rows that full tables hand to an overflow run may bring up to one group each: room for them, bounded by what is likely)
+    const bool want_ov = use_v2 && n_rounds == 1 && !merge && res_slot == 0 && !c->opt.no_overflow_run && n_src >= 1 && n_src <= 4 && N >= (int64_t(1) << 16);
+    const int64_t ov_rows = want_ov ? std::min<int64_t>(std::max<int64_t>(N / 4, 65536), int64_t(1) << 30) : 0;
+    const size_t cap = at.cap = (size_t)std::min<int64_t>(N, (int64_t)P1 * (T + 2) + std::min<int64_t>(ov_rows, std::max<int64_t>(4 * k.est, int64_t(1) << 20))) + (slicing ? side_cap : 0) +
+                                (res_slot == 0 ? (size_t)c->reserve_groups : 0);       // (+ groups a caller will append: the absorb pass's compact spill)
+    ST_TRY(take_result(c, k.rarena, res, cap, k.n_keys_out, partials, partials ? (size_t)(1 + pl.n_states) : (size_t)k.n_aggs));
+    aa.offsets = part.offsets; aa.NB = part.NB; aa.P = (uint32_t)P;
+    aa.T = (uint32_t)T; aa.seed = ep.seed; aa.n_src = n_src; aa.n_states = pl.n_states;
+    aa.n_fin = partials ? 0 : k.n_aggs; aa.partials = partials ? 1 : 0;
+    aa.n_rounds = n_rounds; aa.round_states = ep.round_states; aa.second_pass = pl.needs_second_pass ? 1 : 0;
+    std::memcpy(aa.round_src_begin, ep.round_begin, sizeof aa.round_src_begin);
+    std::memcpy(aa.kinds, pl.kinds, sizeof aa.kinds);
+    aa.out_keys = res.keys; aa.out_null = res.key_null; aa.out_aggs = res.aggs;
+    aa.out_states = res.states; aa.cap = cap; aa.launch_grid = (uint32_t)P + 1;
+    if (slicing || use_v2) {
+        const uint32_t max_tables = (uint32_t)(P1 + max_slices);
+        const uint32_t max_tasks = use_v2 ? 8 * P1 + max_tables : max_tables;
+        const size_t n_state_all = 1 + (size_t)pl.n_states;
+        const bool lean_rounds = use_v2 && n_rounds > 1;
+        const size_t snap_slots = lean_rounds ? (size_t)max_tables * (size_t)(T + 2) : 0;      // every table's key snapshot (launch 0 -> the later rounds)
+        ST_TRY(c->side.ensure(Arena::padded(side_cap * 8) + Arena::padded(side_cap) + n_state_all * Arena::padded(side_cap * 8 + 256) + 8192 +
+                              Arena::padded(snap_slots * 8 + 256) + Arena::padded(snap_slots * 4 + 256) + Arena::padded(snap_slots + 256), c->stream));
+        aa.side_keys = c->side.take<uint64_t>(side_cap);
+        aa.side_null = c->side.take<uint8_t>(side_cap);
+        aa.side_states = c->side.take<uint64_t>(side_cap * n_state_all + 32);
+        aa.side_cap = side_cap;
+        if (lean_rounds) {
+            aa.snap_keys = c->side.take<uint64_t>(snap_slots + 16);
+            aa.snap_pos = c->side.take<uint32_t>(snap_slots + 16);
+            aa.snap_ctrl = c->side.take<uint8_t>(snap_slots + 16);
+            if (!aa.snap_keys || !aa.snap_pos || !aa.snap_ctrl) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "side arena too small (rounds)");
+        }
+        AggTask *tasks = c->work.take<AggTask>(max_tasks + 8);
+        AggTable *tables = c->work.take<AggTable>(max_tables + 8);
+        uint32_t *n_tasks = c->work.take<uint32_t>(64);
+        uint32_t *order = use_v2 && !c->opt.no_table_order ? c->work.take<uint32_t>(2 * (size_t)max_tables + 16) : nullptr;
+        if (!aa.side_keys || !aa.side_null || !aa.side_states || !tasks || !tables || !n_tasks || (use_v2 && !c->opt.no_table_order && !order))
+            return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (slices)");
+        const uint32_t srows = slicing ? (uint32_t)std::min<int64_t>(slice_rows, 0xFFFFFFFFll) : 0xFFFFFFFFu;
+        const uint32_t prows = slicing ? (uint32_t)std::min<int64_t>(piece_rows, 0xFFFFFFFFll) : 0xFFFFFFFFu;
+        if (use_v2) {
+            const SegSource ss{part.offsets, part.NB, part.gbeg, part.gcur, part.gend};
+            hipLaunchKernelGGL(build_tables_kernel, dim3(1), dim3(1024), 0, c->stream, ss, P1, srows, prows, tasks, tables, n_tasks,
+                               max_tasks, max_tables, order, order ? order + max_tables + 8 : nullptr);
+            aa.tables = tables; aa.order = order; aa.launch_grid = max_tables;
+        } else {
+            hipLaunchKernelGGL(build_tasks_kernel, dim3(1), dim3(1024), 0, c->stream, part.offsets, part.NB, P1, srows, prows, tasks, n_tasks, max_tasks);
+            aa.launch_grid = max_tasks;
+        }
+        aa.tasks = tasks; aa.n_tasks = n_tasks;
+    }
+    {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_AGGREGATE);
+        size_t lds = (size_t)(T + 3) * ep.slot_bytes + 192 + (use_v2 ? AGG2_LDS_EXTRA : 0);
+        const int profile = (n_rounds == 1 || use_v2) ? ep.uni_profile : -1;
+        volatile uint32_t *hp = reinterpret_cast<volatile uint32_t *>(c->pinned) + 1040;      // aggregate2's own corner
+        if (use_v2) { hp[4] = 0; aa.host_out = const_cast<uint32_t *>(hp); aa.scatter_flags = sampled ? part.flags : nullptr; }
+        // a full table's unplaced rows go to a buffer and are grouped in a run of their own (AggArgs::ov_keys): an estimate that
+        // was too low costs one small extra run instead of the whole call again
+        at.ov_cap = 0;
+        if (want_ov && c->overflow.ensure((size_t)(1 + n_src) * Arena::padded((size_t)ov_rows * 8 + 256) + (size_t)n_src * Arena::padded((size_t)ov_rows + 256) + 4096, c->stream) == 0) {
+            // (a configured memory limit that leaves no room for the buffer: the call goes on without it — a full table then fails the attempt as before)
+            at.ov_cap = (uint32_t)ov_rows;
+            aa.ov_keys = c->overflow.take<uint64_t>(at.ov_cap);
+            for (int s2 = 0; s2 < n_src; s2++) {
+                aa.ov_vals[s2] = c->overflow.take<uint64_t>(at.ov_cap);
+                aa.ov_valid[s2] = c->overflow.take<uint8_t>(at.ov_cap);
+                if (!aa.ov_vals[s2] || !aa.ov_valid[s2]) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "overflow arena too small");
+            }
+            if (!aa.ov_keys) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "overflow arena too small");
+            aa.ov_cap = at.ov_cap;
+        } else { aa.ov_keys = nullptr; aa.ov_cap = 0; }
+        // keys that arrive in bursts inside their partition (rows clustered in short runs, keys local in position — both behind the exact
+        // partition): every thread folds 8 consecutive rows of the partition in registers (clustered.hip, PARTS) instead of the lean
+        // kernel's row per lane, whose fast path never gets going when a key is new as its burst arrives
+        bool bursts = use_v2 && !sampled && !rs.pre && (c->clumped_rows || c->clustered_rows) && !c->opt.no_burst_kernel;
+        for (int r = 0; r < n_rounds && bursts; r++) bursts = clustered_has(ep.round_begin[r + 1] - ep.round_begin[r], ep.round_prof[r]);
+        const uint32_t grid = (uint32_t)std::min<int64_t>(c->n_cu, aa.launch_grid);
+        if (use_v2 && n_rounds > 1) {
+            // one launch per round over the same tables; only the last one publishes (host_out), the others re-arm the launch counters
+            uint32_t *const publish = aa.host_out;
+            at.polled = true;
+            for (int r = 0; r < n_rounds && at.polled; r++) {
+                const int n_r = ep.round_begin[r + 1] - ep.round_begin[r];
+                aa.cur_round = r; aa.src_base = ep.round_begin[r];
+                aa.host_out = r + 1 == n_rounds ? publish : nullptr;
+                at.polled = bursts ? launch_clustered_parts(c, aa, n_r, ep.round_prof[r], lds, grid) : launch_aggregate2(c, aa, n_r, ep.round_prof[r], lds, grid);
+            }
+            if (!at.polled) return fail(PANDRS_HIP_ERR_COMPUTATION, "lean aggregate: no instantiation for a round of this profile");
+        } else {
+            at.polled = bursts ? launch_clustered_parts(c, aa, n_src, profile, lds, grid) : (use_v2 && launch_aggregate2(c, aa, n_src, profile, lds, grid));
+            if (!at.polled) launch_aggregate(c, aa, ep.max_spr, profile, lds);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    uint32_t *h = reinterpret_cast<uint32_t *>(c->pinned);
+    if (at.polled) {        // aggregate2's last workgroup wrote counters + scatter flag to pinned memory: poll, then fall back
+        volatile uint32_t *hp = reinterpret_cast<volatile uint32_t *>(c->pinned) + 1040;
+        for (int spin = 0; spin < 4000000 && hp[4] != 1; spin++) __builtin_ia32_pause();
+        if (hp[4] == 1) {
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            for (int i = 0; i < 4; i++) h[i] = hp[i];
+            h[6] = hp[6];
+            if (c->opt.agg_ablate == 8) fprintf(stderr, "aggregate2: %u rows took the retry queue\n", hp[5]);
+            return 0;
+        }
+    }
+    if (sampled)         // the scatter's overflow flag rides on the same read-back
+        HIP_TRY(hipMemcpyAsync(aa.counters + 3, part.flags, 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h, aa.counters, 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- one attempt, stage 3, when no table was full: the sliced partitions' records are merged and appended, then the groups of the rows the
+// full tables handed to the overflow buffer.  ATTEMPT_FAILED: those rows held more groups than there is room for, the attempt failed after all.
+static int32_t finish_attempt(pandrs_hip_ctx *c, const EngCall &k, const EnginePlan &ep, const Attempt &at) {
+    const RowSource &rs = k.rs; const Plan &pl = k.pl; const AggArgs &aa = at.aa;
+    GroupbyResult &res = k.res, &r2 = k.res_slot == 0 ? c->gb2 : c->gb3;
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(c->pinned);
+    res.n_groups = h[0]; res.valid = true;
+    const int64_t n_side = h[2];
+    const int64_t n_ov = at.ov_cap ? (int64_t)h[6] : 0;       // (read NOW: the nested runs below reuse the pinned words)
+    if (n_side > 0) {
+        // merge the partial records of the sliced partitions and append their groups
+        RowSource ms = record_source(aa.side_keys, aa.side_null, aa.side_states, at.side_cap, n_side);
+        for (int s2 = 0; s2 < pl.n_src; s2++) {        // First / Last finish with a look-up in the original column
+            ms.fin_data[s2] = rs.fin_data[s2] ? rs.fin_data[s2] : rs.val_data[s2];
+            ms.fin_null_bits[s2] = rs.fin_data[s2] ? rs.fin_null_bits[s2] : rs.val_null_bits[s2];
+        }
+        ST_TRY(merge_records(c, ms, std::min<int64_t>(n_side, k.est), MERGE_NO_SLICE | MERGE_AUTO_PARTITIONS, pl, k.partials, k.n_aggs,
+                             k.key_dtype, 1, k.res_slot + 1));
+        ST_TRY(append_groups(c, res, at.cap, r2, k.partials, pl, k.n_aggs));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (n_ov <= 0) return 0;
+    // the rows the full tables could not place: their keys are in no table, so their groups are simply appended
+    RowSource os;
+    os.n_rows = n_ov;
+    os.key = KeyDesc{aa.ov_keys, nullptr, nullptr, DT_CELL};
+    for (int s2 = 0; s2 < k.n_src; s2++) {
+        os.val_data[s2] = aa.ov_vals[s2];
+        os.val_null_bits[s2] = nullptr;
+        os.val_valid_bytes[s2] = (ep.uni_profile & 1) ? aa.ov_valid[s2] : nullptr;
+    }
+    int32_t st;
+    {
+        NestedRun nested(c);
+        c->opt.partitions = 0; c->opt.no_absorb = 1;
+        c->opt.groups_hint = n_ov <= 4096 ? n_ov : 0;       // (a handful of rows: every row its own group at worst — no sample, no round trip for it)
+        st = run_engine(c, os, pl, /*merge=*/false, k.partials, k.n_aggs, k.key_dtype, 1, k.res_slot + 1);
+    }
+    // the nested run cannot leave one radix level (it is not the call's own run): when the unplaced rows alone hold more
+    // groups than one level takes, THIS attempt has failed — more partitions, or the two-level path, below — and the call
+    // must not fail with the nested run's error (fuzz, round 4: p_max = 24 with 900 K groups)
+    if (st && !c->capacity_exceeded) return st;
+    if (st) c->capacity_exceeded = false;
+    else if ((size_t)res.n_groups + (size_t)r2.n_groups <= at.cap) {
+        ST_TRY(append_groups(c, res, at.cap, r2, k.partials, pl, k.n_aggs));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->timings.retries = at.index + 100;  // (100 + attempt: an overflow run answered)
+        return 0;
+    }
+    res.valid = false;                       // more new groups than the result has room for: the attempt failed after all
+    return ATTEMPT_FAILED;
+}
+
+// Core: groups rs by key and reduces the plan's states.  Result retained in c->gb (res_slot 1, 2: c->gb2, c->gb3, the nested runs').
+int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge,
+                          bool partials, int n_aggs, int key_dtype, int n_keys_out, int res_slot) {
+    if (res_slot < 0 || res_slot > 2) return fail(PANDRS_HIP_ERR_COMPUTATION, "engine nesting too deep");
+    if (c->test_throw_nested && c->quiet > 0) { c->test_throw_nested = false; throw std::bad_alloc(); }     // tests: what a host allocation below could do
+    GroupbyResult &res = res_slot == 0 ? c->gb : (res_slot == 1 ? c->gb2 : c->gb3);
+    Arena &rarena = res_slot == 0 ? c->result : (res_slot == 1 ? c->result2 : c->result3);
+    res = GroupbyResult{};
+    res.n_keys = n_keys_out; res.n_aggs = n_aggs; res.n_state = 1 + pl.n_states; res.partials = partials;
+    res.key_dtype = key_dtype;
+    const int64_t N = rs.n_rows;
+    if (N == 0) { res.valid = true; return 0; }
+    if (N >= (int64_t(1) << 32) - SC_TILE_MAX)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "n_rows %lld exceeds the 2^32 per-call limit", (long long)N);
+
+    std::vector<EngSrc> srcs = build_sources(rs, pl, merge);
+    // (Inside one call, for the row slices of an oversized partition, these merge after all.  First / Last: min / max of the row
+    // index merge like any other state and the value is looked up behind the merge — across shards a row index means nothing.
+    // Std / Var: every slice runs the two passes over its own rows, the merge adds the between-slice term — aggregate.hpp, MergeVar.)
+    const bool nested_slice_merge = merge && !partials && c->quiet > 0;
+    if ((partials || merge) && !pl.mergeable && !nested_slice_merge)
+        return fail(PANDRS_HIP_ERR_OPERATION_FAILED,
+                    "Std/Var/Median/First/Last partial states are not mergeable across shards yet");
+    const int n_src = (int)srcs.size();
+    // (merges of more than 16 states: the record loop of aggregate_kernel<.., MERGE> walks the states at run time; the catch-all instantiation a
+    // Std / Var merge needs keeps register arrays for 16 sources)
+    if (n_src > (merge ? MAX_MERGE_SRC : MAX_SRC) || (merge && n_src > MAX_SRC && pl.needs_second_pass))
+        return fail(PANDRS_HIP_ERR_OPERATION_FAILED, "too many states to merge (%d)", n_src);
+
+    // ---- small calls (launch-bound: the reference's 1 M-row case): two launches, no estimate, no partition
+    if (!merge && !partials && res_slot == 0 && !c->quiet && c->opt.groups_hint <= 0 && !rs.pre)
+        if (const int32_t st = run_small(c, rs, pl, srcs, n_aggs, n_keys_out, res, rarena); st != SMALL_NOT_TAKEN) return st;
+
+    // ---- workspace upper bound so that one ensure() covers the whole call (incl. retries)
+    // the capacity layout of radix_partition_sampled over-allocates the partitioned columns by <= 25 %
+    size_t ws = rs.pre ? engine_workspace_bytes(0, 0, 0) + (size_t(64) << 20)            // the partitioned columns are the producer's
+                       : engine_workspace_bytes(N + N / 4 + 131072, 1 + n_src + (merge ? 1 : 0), n_src);
+    ST_TRY(c->work.ensure(ws, c->stream));
+    int64_t est = rs.pre ? std::max<int64_t>(rs.pre->est_groups, 1) : c->opt.groups_hint;
+    AbsorbDecision ad;
+    ST_TRY(estimate_and_decide_absorb(c, rs, pl, srcs, merge, res_slot, est, ad));
+    if (ad.take)
+        if (const int32_t st = run_absorb(c, rs, pl, srcs, ad.profile, ad.T, est, partials, n_aggs, key_dtype, n_keys_out, res_slot, ad.hot_image); st != ABSORB_NOT_TAKEN) return st;
+    if (c->clustered_rows && !merge && !rs.pre && pl.mergeable && !pl.needs_second_pass && res_slot == 0 && !c->quiet && !c->opt.no_clustered &&
+        !c->opt.generic_aggregate && !c->opt.agg_v1 && !c->opt.deterministic && c->opt.partitions <= 0 && N >= (int64_t(1) << 20))
+        if (const int32_t st = run_clustered(c, rs, pl, srcs, est, partials, n_aggs, key_dtype, n_keys_out, res_slot); st != CLUSTERED_NOT_TAKEN) return st;
+    if (const int32_t st = run_direct(c, rs, pl, srcs, est, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot); st != DIRECT_NOT_TAKEN) return st;
+    EnginePlan ep;
+    ST_TRY(plan_rounds(c, rs, pl, srcs, est, merge, partials, res_slot, ep));
+    if (ep.two_level) return run_two_level(c, rs, pl, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot, est, ep.groups_per_run);
+    const EngCall k{rs, pl, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot, est, n_src, res, rarena};
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(c->pinned);      // the attempt's counters: launch_attempt
     bool sampled_failed = false;       // a capacity-mode run overflowed a region: repeat with the exact histogram
-    bool polled = false;
-    uint32_t ov_cap = 0;
     for (int attempt = 0;; attempt++) {
         c->work.off = 0;
         static const bool trace = std::getenv("PANDRS_HIP_ENGINE_TRACE") != nullptr;       // one line per attempt on stderr (a diagnostic)
         if (trace) fprintf(stderr, "[engine] slot %d merge %d partials %d rows %lld est %lld P %lld T %lld attempt %d lean %d profile %d clustered %d pre %d\n", res_slot, (int)merge, (int)partials,
-                           (long long)N, (long long)est, (long long)P, (long long)T, attempt, (int)use_v2, uni_profile, (int)c->clustered_rows, rs.pre ? 1 : 0);
-        c->timings.n_partitions = P; c->timings.table_slots = T; c->timings.retries = attempt;
-        const uint32_t P1 = (uint32_t)P + 1;
-        // capacity mode (no histogram pass): aggregate2 only (it walks a partition's 8 row ranges), unclustered rows
-        const bool sampled = rs.pre ? true
-                           : use_v2 && !sampled_failed && !c->clustered_rows && !c->clumped_rows && !c->opt.exact_partition && c->opt.shared_cursors &&
-                             c->opt.scatter_threads != 512 && c->opt.scatter_staged && sampled_partition_ok(N, P);
-        if (rs.pre && (!use_v2 || sampled_failed || attempt > 0))      // a full table or a dropped run: the producer must start over
-            return fail(PANDRS_HIP_ERR_COMPUTATION, "pre-partitioned rows: a partition did not fit");
-        const size_t NP = rs.pre ? 0 : sampled ? (size_t)sampled_partition_rows(N, P) : (size_t)N;     // rows of the partitioned columns
-        uint32_t *counters = c->work.take<uint32_t>(64);
-        uint64_t *pkeys = rs.pre ? const_cast<uint64_t *>(rs.pre->pkeys) : c->work.take<uint64_t>(NP);
-        if (!counters || !pkeys) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
-        HIP_TRY(hipMemsetAsync(counters, 0, 64 * 4, c->stream));
-
-        ScatterArgs sa{};
-        sa.key = rs.key; sa.pkeys = pkeys; sa.n_rows = N; sa.P = (uint32_t)P; sa.seed = seed;
-        AggArgs aa{};
-        int64_t *pgsize = nullptr;
-        if (merge) {
-            pgsize = c->work.take<int64_t>(N);
-            if (!pgsize) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
-            sa.mv[sa.n_move++] = MoveDesc{rs.merge_gsize ? (const void *)rs.merge_gsize : (const void *)rs.merge_states, pgsize, 0, 0};
-        }
-        // LDS index of every state inside its round
-        int8_t st_round[MAX_STATES], st_lds[MAX_STATES];
-        for (int k = 0; k < MAX_STATES; k++) { st_round[k] = -1; st_lds[k] = -1; }
-        // aggregate2's fixed LDS state order: the adds of source 0..n-1, then per source its min-type states
-        // (min, ~max), then the non-null counts
-        for (int r = 0; r < n_rounds; r++) {
-            int next = 0;
-            const int n_r = round_begin[r + 1] - round_begin[r];          // (the order holds inside every round of the lean kernel)
-            const int rp = round_prof[r];                                   // (rounds grouped by profile: each round its own)
-            const int v2_mm = use_v2 ? ((rp >> 2) & 1) + ((rp >> 3) & 1) : 0;
-            const int v2_mbase = use_v2 && ((rp >> 1) & 1) ? n_r : 0;
-            int v2_next_nn = v2_mbase + n_r * v2_mm;
-            for (int s = round_begin[r]; s < round_begin[r + 1]; s++) {
-                EngSrc &e = srcs[s];
-                uint64_t *pv = rs.pre ? const_cast<uint64_t *>(rs.pre->pvals[s]) : c->work.take<uint64_t>(NP);
-                if (!pv) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
-                sa.mv[sa.n_move++] = MoveDesc{e.data, pv, (e.rowidx && !e.data) ? 5 : 0, 0};
-                uint8_t *pvalid = nullptr;
-                if (e.null_bits || e.valid_bytes) {
-                    pvalid = c->work.take<uint8_t>(NP);
-                    if (!pvalid) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small");
-                    sa.mv[sa.n_move++] = e.null_bits ? MoveDesc{e.null_bits, pvalid, 1, 0} : MoveDesc{e.valid_bytes, pvalid, 2, 0};
-                }
-                SrcDev &sd = aa.src[s];
-                sd = SrcDev{pv, pvalid, e.kind, -1, -1, -1, -1, -1, -1, {0}};
-                auto place = [&](int8_t abs_id, int8_t &lds_id) {
-                    if (abs_id < 0) return;
-                    st_round[abs_id] = (int8_t)r; st_lds[abs_id] = (int8_t)next; lds_id = (int8_t)next; next++;
-                };
-                if (use_v2) {
-                    auto put = [&](int8_t abs_id, int8_t &lds_id, int at) {
-                        if (abs_id < 0) return;
-                        st_round[abs_id] = (int8_t)r; st_lds[abs_id] = (int8_t)at; lds_id = (int8_t)at;
-                    };
-                    const int sl = s - round_begin[r];
-                    put(e.st_add, sd.st_add, sl);
-                    put(e.st_min, sd.st_min, v2_mbase + sl * v2_mm);
-                    put(e.st_max, sd.st_max, v2_mbase + sl * v2_mm + v2_mm - 1);
-                    if (e.st_nn >= 0) put(e.st_nn, sd.st_nn, v2_next_nn++);
-                    continue;
-                }
-                place(e.st_add, sd.st_add); place(e.st_min, sd.st_min); place(e.st_max, sd.st_max); place(e.st_nn, sd.st_nn);
-                place(e.st_fadd, sd.st_fadd); place(e.st_ssq, sd.st_ssq);
-            }
-        }
-        if (merge && pl.needs_second_pass) {
-            if (n_rounds != 1) return fail(PANDRS_HIP_ERR_COMPUTATION, "Std / Var records merge in one round only");
-            for (int s2 = 0; s2 < pl.n_src; s2++) {
-                if (pl.st_ssq[s2] < 0) continue;
-                if (aa.n_mvar >= MAX_MERGE_VAR) return fail(PANDRS_HIP_ERR_COMPUTATION, "too many Std / Var columns to merge");
-                const int8_t ssum = pl.src_kind[s2] == 0 ? pl.st_add[s2] : pl.st_fadd[s2], snn = pl.st_nn[s2];
-                MergeVar &mv = aa.mvar[aa.n_mvar++];
-                mv.ssq = st_lds[pl.st_ssq[s2]]; mv.sum = st_lds[ssum]; mv.nn = snn >= 0 ? st_lds[snn] : (int8_t)-1;
-                mv.sum_col = aa.src[ssum].vals; mv.nn_col = snn >= 0 ? aa.src[snn].vals : nullptr;
-            }
-        }
-        PartInfo part;
-        if (rs.pre) part = rs.pre->part;
-        else if (sampled) ST_TRY(radix_partition_sampled(c, sa, &part, PANDRS_HIP_PHASE_HISTOGRAM, PANDRS_HIP_PHASE_SCATTER));
-        else ST_TRY(radix_partition(c, sa, &part, PANDRS_HIP_PHASE_HISTOGRAM, PANDRS_HIP_PHASE_SCAN, PANDRS_HIP_PHASE_SCATTER));
-        const uint32_t NB = part.NB;
-        uint32_t *offsets = part.offsets;
-
-        // ---- aggregate
-        // oversized partitions (a hot key, heavy skew) are cut into row slices for separate workgroups
-        int n_var_src = 0;
-        for (int s2 = 0; s2 < pl.n_src; s2++) n_var_src += pl.st_ssq[s2] >= 0;
-        const bool slicing = !c->opt.no_slice && (pl.mergeable || (!partials && !merge && n_var_src <= MAX_MERGE_VAR)) && (n_rounds == 1 || (use_v2 && !partials)) && pl.n_states <= MAX_MERGE_SRC;      // (the lean kernel's rounds fill a piece's record round by round)
-        const int64_t slice_rows = c->opt.slice_rows > 0 ? c->opt.slice_rows
-                                 : auto_slice_rows > 0 ? auto_slice_rows
-                                                       : std::max<int64_t>(int64_t(1) << 18, (c->opt.wide_slices ? 4 : (c->opt.slice_over > 0 ? c->opt.slice_over : 2)) * (N / std::max<int64_t>(P, 1)));
-        // (cut when far above the average, into pieces of the average size: build_tasks_kernel.  A forced or mid-cardinality
-        // slice length is both at once.)
-        const int64_t piece_rows = (c->opt.slice_rows > 0 || auto_slice_rows > 0 || c->opt.wide_slices) ? slice_rows
-                                 : std::min<int64_t>(slice_rows, std::max<int64_t>(int64_t(1) << 16, N / std::max<int64_t>(P, 1)));
-        const int64_t max_slices = slicing ? N / piece_rows + N / slice_rows + 2 : 0;       // slices of multi-slice partitions
-        const size_t side_cap = (size_t)max_slices * (size_t)(T + 2);
-        // (rows that full tables hand to an overflow run may bring up to one group each: room for them, bounded by what is likely)
-        const bool want_ov = use_v2 && n_rounds == 1 && !merge && res_slot == 0 && !c->opt.no_overflow_run && n_src >= 1 && n_src <= 4 && N >= (int64_t(1) << 16);
-        const int64_t ov_rows = want_ov ? std::min<int64_t>(std::max<int64_t>(N / 4, 65536), int64_t(1) << 30) : 0;
-        size_t cap = (size_t)std::min<int64_t>(N, (int64_t)P1 * (T + 2) + std::min<int64_t>(ov_rows, std::max<int64_t>(4 * est, int64_t(1) << 20))) + (slicing ? side_cap : 0) +
-                     (res_slot == 0 ? (size_t)c->reserve_groups : 0);       // (+ groups a caller will append: the absorb pass's compact spill)
-        size_t out_cols = partials ? (size_t)(1 + pl.n_states) : (size_t)n_aggs;
-        ST_TRY(rarena.ensure((size_t)n_keys_out * (Arena::padded(cap * 8) + Arena::padded(cap)) + std::max<size_t>(out_cols, 1) * Arena::padded(cap * 8 + 256) + 8192, c->stream));
-        res.cap = (int64_t)cap;
-        res.keys = rarena.take<uint64_t>(cap * n_keys_out);      // [n_keys][cap]; row 0 holds the engine's cell
-        res.key_null = rarena.take<uint8_t>(cap * n_keys_out);
-        if (partials) res.states = rarena.take<uint64_t>(cap * out_cols + 32);
-        else res.aggs = rarena.take<double>(cap * std::max<size_t>(out_cols, 1) + 32);
-        if (!res.keys || !res.key_null || (!res.states && !res.aggs))
-            return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "result arena too small");
-        aa.pkeys = pkeys; aa.offsets = offsets; aa.pgsize = pgsize; aa.NB = NB; aa.P = (uint32_t)P;
-        aa.T = (uint32_t)T; aa.seed = seed; aa.n_src = n_src; aa.n_states = pl.n_states;
-        aa.n_fin = partials ? 0 : n_aggs; aa.partials = partials ? 1 : 0;
-        aa.n_rounds = n_rounds; aa.round_states = round_states; aa.second_pass = pl.needs_second_pass ? 1 : 0;
-        std::memcpy(aa.round_src_begin, round_begin, sizeof aa.round_src_begin);
-        std::memcpy(aa.kinds, pl.kinds, sizeof aa.kinds);
-        std::memcpy(aa.st_round, st_round, sizeof st_round);
-        std::memcpy(aa.st_lds, st_lds, sizeof st_lds);
-        for (int f = 0; f < n_aggs && !partials; f++) {
-            FinDev &fd = aa.fin[f];
-            fd = FinDev{};
-            fd.op = pl.fin_op[f]; fd.kind = pl.fin_kind[f];
-            fd.st_add = fd.st_nn = fd.st_min = fd.st_max = fd.st_ssq = fd.st_fadd = fd.rowsrc_min = fd.rowsrc_max = -1;
-            int s = pl.fin_src[f];
-            if (s < 0) continue;                                   // COUNT: round 0, group size only
-            auto lds_of = [&](int8_t abs_id) -> int8_t { return abs_id < 0 ? (int8_t)-1 : st_lds[abs_id]; };
-            fd.st_add = lds_of(pl.st_add[s]); fd.st_nn = lds_of(pl.st_nn[s]);
-            fd.st_min = lds_of(pl.st_min[s]); fd.st_max = lds_of(pl.st_max[s]);
-            fd.st_ssq = lds_of(pl.st_ssq[s]); fd.st_fadd = lds_of(pl.st_fadd[s]);
-            int8_t any = pl.st_add[s] >= 0 ? pl.st_add[s] : (pl.st_min[s] >= 0 ? pl.st_min[s] : (pl.st_max[s] >= 0 ? pl.st_max[s] : (pl.st_ssq[s] >= 0 ? pl.st_ssq[s] : (int8_t)-1)));
-            fd.round = any >= 0 ? st_round[any] : 0;
-            if (fd.op == PANDRS_HIP_AGG_FIRST || fd.op == PANDRS_HIP_AGG_LAST) {
-                fd.rowsrc_min = st_lds[pl.st_firstrow]; fd.rowsrc_max = st_lds[pl.st_lastrow];
-                fd.round = st_round[pl.st_firstrow];
-                fd.col_data = rs.fin_data[s] ? rs.fin_data[s] : rs.val_data[s];
-                fd.col_null = rs.fin_data[s] ? rs.fin_null_bits[s] : rs.val_null_bits[s];
-            }
-        }
-        aa.out_keys = res.keys; aa.out_null = res.key_null; aa.out_aggs = res.aggs;
-        aa.out_states = res.states; aa.cap = cap; aa.counters = counters; aa.launch_grid = (uint32_t)P + 1;
-        if (slicing || use_v2) {
-            const uint32_t max_tables = (uint32_t)(P1 + max_slices);
-            const uint32_t max_tasks = use_v2 ? 8 * P1 + max_tables : max_tables;
-            const size_t n_state_all = 1 + (size_t)pl.n_states;
-            const bool lean_rounds = use_v2 && n_rounds > 1;
-            const size_t snap_slots = lean_rounds ? (size_t)max_tables * (size_t)(T + 2) : 0;      // every table's key snapshot (launch 0 -> the later rounds)
-            ST_TRY(c->side.ensure(Arena::padded(side_cap * 8) + Arena::padded(side_cap) + n_state_all * Arena::padded(side_cap * 8 + 256) + 8192 +
-                                  Arena::padded(snap_slots * 8 + 256) + Arena::padded(snap_slots * 4 + 256) + Arena::padded(snap_slots + 256), c->stream));
-            aa.side_keys = c->side.take<uint64_t>(side_cap);
-            aa.side_null = c->side.take<uint8_t>(side_cap);
-            aa.side_states = c->side.take<uint64_t>(side_cap * n_state_all + 32);
-            aa.side_cap = side_cap;
-            if (lean_rounds) {
-                aa.snap_keys = c->side.take<uint64_t>(snap_slots + 16);
-                aa.snap_pos = c->side.take<uint32_t>(snap_slots + 16);
-                aa.snap_ctrl = c->side.take<uint8_t>(snap_slots + 16);
-                if (!aa.snap_keys || !aa.snap_pos || !aa.snap_ctrl) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "side arena too small (rounds)");
-            }
-            AggTask *tasks = c->work.take<AggTask>(max_tasks + 8);
-            AggTable *tables = c->work.take<AggTable>(max_tables + 8);
-            uint32_t *n_tasks = c->work.take<uint32_t>(64);
-            uint32_t *order = use_v2 && !c->opt.no_table_order ? c->work.take<uint32_t>(2 * (size_t)max_tables + 16) : nullptr;
-            if (!aa.side_keys || !aa.side_null || !aa.side_states || !tasks || !tables || !n_tasks || (use_v2 && !c->opt.no_table_order && !order))
-                return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (slices)");
-            const uint32_t srows = slicing ? (uint32_t)std::min<int64_t>(slice_rows, 0xFFFFFFFFll) : 0xFFFFFFFFu;
-            const uint32_t prows = slicing ? (uint32_t)std::min<int64_t>(piece_rows, 0xFFFFFFFFll) : 0xFFFFFFFFu;
-            if (use_v2) {
-                const SegSource ss{offsets, NB, part.gbeg, part.gcur, part.gend};
-                hipLaunchKernelGGL(build_tables_kernel, dim3(1), dim3(1024), 0, c->stream, ss, P1, srows, prows, tasks, tables, n_tasks,
-                                   max_tasks, max_tables, order, order ? order + max_tables + 8 : nullptr);
-                aa.tables = tables; aa.order = order; aa.launch_grid = max_tables;
-            } else {
-                hipLaunchKernelGGL(build_tasks_kernel, dim3(1), dim3(1024), 0, c->stream, offsets, NB, P1, srows, prows, tasks, n_tasks, max_tasks);
-                aa.launch_grid = max_tasks;
-            }
-            aa.tasks = tasks; aa.n_tasks = n_tasks;
-        }
-        {
-            PhaseTimer pt(c, PANDRS_HIP_PHASE_AGGREGATE);
-            size_t lds = (size_t)(T + 3) * slot_bytes + 192 + (use_v2 ? AGG2_LDS_EXTRA : 0);
-            const int profile = (n_rounds == 1 || use_v2) ? uni_profile : -1;
-            volatile uint32_t *hp = reinterpret_cast<volatile uint32_t *>(c->pinned) + 1040;      // aggregate2's own corner
-            if (use_v2) { hp[4] = 0; aa.host_out = const_cast<uint32_t *>(hp); aa.scatter_flags = sampled ? part.flags : nullptr; }
-            // a full table's unplaced rows go to a buffer and are grouped in a run of their own (AggArgs::ov_keys): an estimate that
-            // was too low costs one small extra run instead of the whole call again
-            ov_cap = 0;
-            if (want_ov && c->overflow.ensure((size_t)(1 + n_src) * Arena::padded((size_t)ov_rows * 8 + 256) + (size_t)n_src * Arena::padded((size_t)ov_rows + 256) + 4096, c->stream) == 0) {
-                // (a configured memory limit that leaves no room for the buffer: the call goes on without it — a full table then fails the attempt as before)
-                ov_cap = (uint32_t)ov_rows;
-                aa.ov_keys = c->overflow.take<uint64_t>(ov_cap);
-                for (int s2 = 0; s2 < n_src; s2++) {
-                    aa.ov_vals[s2] = c->overflow.take<uint64_t>(ov_cap);
-                    aa.ov_valid[s2] = c->overflow.take<uint8_t>(ov_cap);
-                    if (!aa.ov_vals[s2] || !aa.ov_valid[s2]) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "overflow arena too small");
-                }
-                if (!aa.ov_keys) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "overflow arena too small");
-                aa.ov_cap = ov_cap;
-            } else { aa.ov_keys = nullptr; aa.ov_cap = 0; }
-            // keys that arrive in bursts inside their partition (rows clustered in short runs, keys local in position — both behind the exact
-            // partition): every thread folds 8 consecutive rows of the partition in registers (clustered.hip, PARTS) instead of the lean
-            // kernel's row per lane, whose fast path never gets going when a key is new as its burst arrives
-            bool bursts = use_v2 && !sampled && !rs.pre && (c->clumped_rows || c->clustered_rows) && !c->opt.no_burst_kernel;
-            for (int r = 0; r < n_rounds && bursts; r++) bursts = clustered_has(round_begin[r + 1] - round_begin[r], round_prof[r]);
-            if (use_v2 && n_rounds > 1) {
-                // one launch per round over the same tables; only the last one publishes (host_out), the others re-arm the launch counters
-                uint32_t *const publish = aa.host_out;
-                polled = true;
-                for (int r = 0; r < n_rounds && polled; r++) {
-                    aa.cur_round = r; aa.src_base = round_begin[r];
-                    aa.host_out = r + 1 == n_rounds ? publish : nullptr;
-                    polled = bursts ? launch_clustered_parts(c, aa, round_begin[r + 1] - round_begin[r], round_prof[r], lds, (uint32_t)std::min<int64_t>(c->n_cu, aa.launch_grid))
-                                    : launch_aggregate2(c, aa, round_begin[r + 1] - round_begin[r], round_prof[r], lds, (uint32_t)std::min<int64_t>(c->n_cu, aa.launch_grid));
-                }
-                if (!polled) return fail(PANDRS_HIP_ERR_COMPUTATION, "lean aggregate: no instantiation for a round of this profile");
-            } else {
-            polled = bursts ? launch_clustered_parts(c, aa, n_src, profile, lds, (uint32_t)std::min<int64_t>(c->n_cu, aa.launch_grid))
-                            : (use_v2 && launch_aggregate2(c, aa, n_src, profile, lds, (uint32_t)std::min<int64_t>(c->n_cu, aa.launch_grid)));
-            if (!polled) launch_aggregate(c, aa, max_spr, profile, lds);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        uint32_t *h = reinterpret_cast<uint32_t *>(c->pinned);
-        bool have = false;
-        if (polled) {        // aggregate2's last workgroup wrote counters + scatter flag to pinned memory: poll, then fall back
-            volatile uint32_t *hp = reinterpret_cast<volatile uint32_t *>(c->pinned) + 1040;
-            for (int spin = 0; spin < 4000000 && hp[4] != 1; spin++) __builtin_ia32_pause();
-            if (hp[4] == 1) {
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                for (int i = 0; i < 4; i++) h[i] = hp[i];
-                h[6] = hp[6];
-                if (c->opt.agg_ablate == 8) fprintf(stderr, "aggregate2: %u rows took the retry queue\n", hp[5]);
-                have = true;
-            }
-        }
-        if (!have) {
-            if (sampled)         // the scatter's overflow flag rides on the same read-back
-                HIP_TRY(hipMemcpyAsync(counters + 3, part.flags, 4, hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(h, counters, 32, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        if (sampled && h[3]) {           // a region's sampled capacity was too small (skew the sample did not show)
+                           (long long)N, (long long)est, (long long)ep.P, (long long)ep.T, attempt, (int)ep.use_v2, ep.uni_profile, (int)c->clustered_rows, rs.pre ? 1 : 0);
+        c->timings.n_partitions = ep.P; c->timings.table_slots = ep.T; c->timings.retries = attempt;
+        Attempt at;
+        at.index = attempt; at.exact = sampled_failed;
+        ST_TRY(lay_out_and_partition(c, k, ep, srcs, at));
+        ST_TRY(launch_attempt(c, k, ep, at));
+        if (at.sampled && h[3]) {           // a region's sampled capacity was too small (skew the sample did not show)
             sampled_failed = true;
             attempt--;
             continue;
         }
-        if (h[1] == 0) {
-            res.n_groups = h[0]; res.valid = true;
-            const int64_t n_side = h[2];
-            const int64_t n_ov = ov_cap ? (int64_t)h[6] : 0;       // (read NOW: the nested runs below reuse the pinned words)
-            if (n_side > 0) {
-                // merge the partial records of the sliced partitions and append their groups
-                RowSource ms = record_source(aa.side_keys, aa.side_null, aa.side_states, side_cap, n_side);
-                for (int s2 = 0; s2 < pl.n_src; s2++) {        // First / Last finish with a look-up in the original column
-                    ms.fin_data[s2] = rs.fin_data[s2] ? rs.fin_data[s2] : rs.val_data[s2];
-                    ms.fin_null_bits[s2] = rs.fin_data[s2] ? rs.fin_null_bits[s2] : rs.val_null_bits[s2];
-                }
-                ST_TRY(merge_records(c, ms, std::min<int64_t>(n_side, est), MERGE_NO_SLICE | MERGE_AUTO_PARTITIONS, pl, partials, n_aggs,
-                                     key_dtype, 1, res_slot + 1));
-                GroupbyResult &r2 = res_slot == 0 ? c->gb2 : c->gb3;
-                ST_TRY(append_groups(c, res, cap, r2, partials, pl, n_aggs));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            }
-            if (n_ov > 0) {
-                // the rows the full tables could not place: their keys are in no table, so their groups are simply appended
-                RowSource os;
-                os.n_rows = n_ov;
-                os.key = KeyDesc{aa.ov_keys, nullptr, nullptr, DT_CELL};
-                for (int s2 = 0; s2 < n_src; s2++) {
-                    os.val_data[s2] = aa.ov_vals[s2];
-                    os.val_null_bits[s2] = nullptr;
-                    os.val_valid_bytes[s2] = (uni_profile & 1) ? aa.ov_valid[s2] : nullptr;
-                }
-                int32_t st;
-                {
-                    NestedRun nested(c);
-                    c->opt.partitions = 0; c->opt.no_absorb = 1;
-                    c->opt.groups_hint = n_ov <= 4096 ? n_ov : 0;       // (a handful of rows: every row its own group at worst — no sample, no round trip for it)
-                    st = run_engine(c, os, pl, /*merge=*/false, partials, n_aggs, key_dtype, 1, res_slot + 1);
-                }
-                // the nested run cannot leave one radix level (it is not the call's own run): when the unplaced rows alone hold more
-                // groups than one level takes, THIS attempt has failed — more partitions, or the two-level path, below — and the call
-                // must not fail with the nested run's error (fuzz, round 4: p_max = 24 with 900 K groups)
-                if (st && !c->capacity_exceeded) return st;
-                GroupbyResult &r2 = res_slot == 0 ? c->gb2 : c->gb3;
-                if (st) c->capacity_exceeded = false;
-                else if ((size_t)res.n_groups + (size_t)r2.n_groups <= cap) {
-                    ST_TRY(append_groups(c, res, cap, r2, partials, pl, n_aggs));
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    c->timings.retries = attempt + 100;  // (100 + attempt: an overflow run answered)
-                    return 0;
-                }
-                res.valid = false;                       // more new groups than the result has room for: the attempt failed after all
-                h[1] = 1;
-            } else return 0;
-        }
-        if (h[1] == 0) return 0;
-        if (P >= P_LIMIT) {
+        if (h[1] == 0)
+            if (const int32_t st = finish_attempt(c, k, ep, at); st != ATTEMPT_FAILED) return st;
+        if (ep.P >= ep.P_LIMIT) {
             if (c->opt.partitions <= 0 && res_slot == 0 && !c->quiet)      // the estimate was far too low: two-level with a safe bound
-                return run_two_level(c, rs, pl, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot, N,
-                                     (int64_t)((double)P_LIMIT * 0.6 * (double)T * LOAD));
+                return run_two_level(c, rs, pl, merge, partials, n_aggs, key_dtype, n_keys_out, res_slot, N, ep.groups_per_run);
             c->capacity_exceeded = true;
             return fail(PANDRS_HIP_ERR_COMPUTATION,
                         "group cardinality exceeds the radix capacity (%lld partitions x %lld slots)",
-                        (long long)P_LIMIT, (long long)T);
+                        (long long)ep.P_LIMIT, (long long)ep.T);
         }
-        P = std::min<int64_t>(P * 4, P_LIMIT);
+        ep.P = std::min<int64_t>(ep.P * 4, ep.P_LIMIT);
     }
 }
 
@@ -2034,17 +2041,10 @@ static int32_t run_two_level(pandrs_hip_ctx *c, const RowSource &rs, const Plan 
 
     // ---- result arrays for the concatenation (every row could be its own group)
     const size_t cap = (size_t)N + 8 + (res_slot == 0 ? (size_t)c->reserve_groups : 0);
-    const size_t out_cols = partials ? (size_t)(1 + pl.n_states) : (size_t)std::max(n_aggs, 1);
     res = GroupbyResult{};
     res.n_keys = n_keys_out; res.n_aggs = n_aggs; res.n_state = 1 + pl.n_states; res.partials = partials;
     res.key_dtype = key_dtype;
-    ST_TRY(rarena.ensure((size_t)n_keys_out * (Arena::padded(cap * 8) + Arena::padded(cap)) + out_cols * Arena::padded(cap * 8 + 256) + 8192, c->stream));
-    res.cap = (int64_t)cap;
-    res.keys = rarena.take<uint64_t>(cap * n_keys_out);
-    res.key_null = rarena.take<uint8_t>(cap * n_keys_out);
-    if (partials) res.states = rarena.take<uint64_t>(cap * out_cols + 32);
-    else res.aggs = rarena.take<double>(cap * out_cols + 32);
-    if (!res.keys || !res.key_null || (!res.states && !res.aggs)) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "result arena too small");
+    ST_TRY(take_result(c, rarena, res, cap, n_keys_out, partials, partials ? (size_t)(1 + pl.n_states) : (size_t)n_aggs));
 
     int32_t st = 0;
     c->capacity_exceeded = false;
