@@ -698,6 +698,60 @@ typedef enum pandrs_hip_rank_method {   /* RankMethod, types.rs:48-59, same orde
 int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                         int32_t method, int32_t out_mem_space, double *out);
 
+/* ---- missing cells of one numeric column: ffill, bfill, interpolate, fillna -------------------------------------------------
+ * PandasCompatExt::fillna (src/dataframe/pandas_compat/functions.rs:789), fillna_method (:811-868), interpolate (:870-918),
+ * ffill / bfill (:3626-3683); known answers :4751-4970, :8007-8050.  A cell is MISSING when its null bit is set or, for an F64
+ * column, when it is NaN (the reference's is_nan() marker); an I64 cell is missing only by its null bit.  Everything else is
+ * valid: +-inf and -0.0 too.  A valid row's cell is copied unchanged.  For a missing row i:
+ *   FFILL   the cell of the nearest valid row before i, bit for bit; a row with no valid row before it stays missing.
+ *   BFILL   the mirror image: the nearest valid row after i.
+ *   LINEAR  between the nearest valid rows p < i < q: a + ((b - a) * (double)(i - p)) / (double)(q - p), a and b the cells as
+ *           f64 (`v as f64` for I64): the reference's expression (:889-894) in that association, every operation rounded on its
+ *           own (no fused multiply-add).  Rows before the first or after the last valid row stay missing.  The output is F64
+ *           whatever the column: a valid I64 cell is written as (double)v.
+ *   VALUE   the 8-byte cell fill_bits, as is (an I64 value, or the bits of an f64).  An F64 fill_bits that is NaN leaves the
+ *           rows missing, as the reference's fillna(NaN) does.
+ * The output has the column's dtype except under LINEAR.  A row that stays missing is written as the canonical quiet NaN
+ * 0x7FF8000000000000 for an F64 output and as 0 for an I64 output, and its bit is set in out_null_mask.  An interior LINEAR row
+ * whose arithmetic gives NaN (inf - inf) is NOT missing: its bit is 0.  *out_n_missing = the rows still missing.
+ * How (fill.hip): (1) one stream over the column and its mask writes one valid bit per row (a wave ballot is the 64-row word)
+ * and every tile's first and last valid row; for I64 only the mask is read; (2) one small workgroup carries "the last valid row
+ * to the left" and "the first valid row to the right" across the tile summaries, "none" kept apart from row 0 (row + 1 on the
+ * left, 0xFFFFFFFF on the right); every hand-off between workgroups is a kernel boundary, no workgroup waits for another; (3) per
+ * tile the words give each row its source (highest set bit at or below it / lowest set bit at or above it, else the carry), a
+ * missing row gathers it (LINEAR: both ends) and the ballot of "still missing" is the output mask word.  VALUE is one kernel; an
+ * I64 column without a mask has nothing missing and is copied (LINEAR: converted).
+ * Geometry (tests read it): fill_tile_rows = 2048 rows per workgroup iteration, fill_blocks_per_cu = 4, grid =
+ * min(fill_blocks_per_cu x compute units, ceil(n_rows / fill_tile_rows)) workgroups striding over the tiles.
+ * Deviations:
+ *  - the reference casts every numeric column to f64 (get_column_numeric_values) and has no null mask on this path: a missing
+ *    value there is a NaN cell only.  Here a null bit counts as missing too, and the cell under it is never a source.
+ *  - here I64 stays I64 under FFILL / BFILL / VALUE, exactly; only LINEAR answers in f64.
+ * Buffers: col is I64 or F64, with or without a mask; any other dtype: PANDRS_HIP_ERR_TYPE_MISMATCH.  Host columns and outputs
+ * are staged; device and resident columns are read in place.  Data and out_data are 8-byte aligned (16 is not required); the
+ * masks may sit at any byte offset, input bits past n_rows are ignored.  out_data receives n_rows x 8 bytes.  out_null_mask
+ * receives exactly ceil(n_rows / 8) bytes, bits past n_rows in the last byte 0, and no byte beyond is touched (the words are
+ * stored bytewise); it may be NULL, except where the output is I64 and the column has a mask and the method is not VALUE (the
+ * data alone could not tell a missing row from a 0): PANDRS_HIP_ERR_INVALID_ARGUMENT.  out_data or out_null_mask overlapping the
+ * column's data or mask in the same memory space: PANDRS_HIP_ERR_INVALID_ARGUMENT (missing rows gather from their neighbours, so
+ * the call cannot run in place).  out_n_missing is a host pointer and may be NULL.
+ * pandrs_hip_get_timings: the phase is PANDRS_HIP_PHASE_AGGREGATE, n_partitions is 0, algorithmic_bytes counts the streams run.
+ * Workspace, sized up front in one arena: n_rows / 8 bytes of valid bits plus 16 bytes per fill_tile_rows rows plus the counter:
+ * about 0.13 bytes per row (VALUE and an unmasked I64 column: the counter only); staging: a host column and host outputs.  A
+ * memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
+ * col / out_data, a method outside 0 .. 3 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written,
+ * *out_n_missing = 0.
+ * Out of scope: limit=, dropna / isna / count_na, non-linear interpolation, group-wise fills, String and Boolean columns, the
+ * legacy string frame, TimeSeries::fillna_forward. */
+typedef enum pandrs_hip_fill_method {
+    PANDRS_HIP_FILL_FFILL = 0, PANDRS_HIP_FILL_BFILL = 1, PANDRS_HIP_FILL_LINEAR = 2, PANDRS_HIP_FILL_VALUE = 3
+} pandrs_hip_fill_method;
+
+int32_t pandrs_hip_fill(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                        int32_t method, uint64_t fill_bits, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,
+                        int64_t *out_n_missing);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

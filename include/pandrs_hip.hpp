@@ -348,6 +348,34 @@ public:
         }
         return ranks;
     }
+    // ffill / bfill / fillna_method / interpolate / fillna (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:789-918,
+    // :3626-3683): a NEW frame from one pandrs_hip_fill call, the named column replaced (same name, same position; Float64
+    // after interpolate; a null mask only when rows are still missing), the other columns copied as they are.  A cell is
+    // missing when its null bit is set or, for Float64, when it is NaN.  Errors before any device call: ColumnNotFound, Type
+    // (a String or Boolean column), InvalidValue (an unknown fill method; a fillna value an Int64 column cannot hold).
+    // Deviations (pandrs_hip.h): the reference casts every numeric column to f64 and knows no null mask here; Int64 stays
+    // Int64 under ffill / bfill / fillna.
+    OptimizedDataFrame ffill(const std::string &column_name) const { return fill(column_name, PANDRS_HIP_FILL_FFILL, 0); }
+    OptimizedDataFrame bfill(const std::string &column_name) const { return fill(column_name, PANDRS_HIP_FILL_BFILL, 0); }
+    OptimizedDataFrame interpolate(const std::string &column_name) const { return fill(column_name, PANDRS_HIP_FILL_LINEAR, 0); }
+    OptimizedDataFrame fillna_method(const std::string &column_name, const std::string &method) const {
+        (void)column(column_name);
+        if (method == "ffill" || method == "forward") return ffill(column_name);
+        if (method == "bfill" || method == "backward") return bfill(column_name);
+        throw Error(Error::InvalidValue, "Invalid fill method: '" + method + "'. Use 'ffill' or 'bfill'.");     // functions.rs:846-851
+    }
+    OptimizedDataFrame fillna(const std::string &column_name, double value) const {
+        const Column &c = column(column_name);
+        uint64_t bits = 0;
+        if (c.index() == 0) {
+            if (!(value >= -9223372036854775808.0 && value < 9223372036854775808.0) || value != std::floor(value))
+                throw Error(Error::InvalidValue, "an Int64 column is filled with an integer that fits int64");
+            bits = (uint64_t)(int64_t)value;
+        } else {
+            std::memcpy(&bits, &value, 8);
+        }
+        return fill(column_name, PANDRS_HIP_FILL_VALUE, bits);
+    }
     // describe_all (stats.rs:157-171): every Int64 / Float64 column; one whose describe fails with InvalidValue is left out
     std::map<std::string, StatDescribe> describe_all() const {
         std::map<std::string, StatDescribe> results;
@@ -483,6 +511,30 @@ public:
 private:
     size_t row_count_ = 0;
     std::shared_ptr<detail::ResidentSet> resident_;
+
+    // one pandrs_hip_fill call (method = pandrs_hip_fill_method) -> the frame with the named column replaced
+    OptimizedDataFrame fill(const std::string &column_name, int32_t method, uint64_t fill_bits) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        if (!row_count_) return *this;                      // an equal frame, no device call
+        const bool out_i64 = c.index() == 0 && method != PANDRS_HIP_FILL_LINEAR;
+        Int64Column oi;
+        Float64Column of;
+        std::vector<uint8_t> mask((row_count_ + 7) / 8);
+        int64_t missing = 0;
+        if (out_i64) oi.data.resize(row_count_); else of.data.resize(row_count_);
+        const pandrs_hip_column v = view_of(column_name);
+        detail::check(pandrs_hip_fill(detail::context(), mem_space(), &v, (int64_t)row_count_, method, fill_bits, PANDRS_HIP_MEM_HOST,
+                                      out_i64 ? (void *)oi.data.data() : (void *)of.data.data(), mask.data(), &missing));
+        if (missing) (out_i64 ? oi.null_mask : of.null_mask) = std::move(mask);
+        OptimizedDataFrame out;
+        for (size_t k = 0; k < columns.size(); k++) {
+            if (column_names[k] != column_name) out.add_column(column_names[k], columns[k]);
+            else if (out_i64) out.add_column(column_names[k], std::move(oi));
+            else out.add_column(column_names[k], std::move(of));
+        }
+        return out;
+    }
 
     void window_column(const std::string &name) const {
         const Column &c = column(name);

@@ -504,6 +504,14 @@ int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
     return pandrs::rank_entry(ctx, mem_space, col, n_rows, method, out_mem_space, out);
 } catch (...) { return pandrs::on_exception("pandrs_hip_rank"); }
 
+int32_t pandrs_hip_fill(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                        int32_t method, uint64_t fill_bits, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,
+                        int64_t *out_n_missing) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "fill: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::fill_entry(ctx, mem_space, col, n_rows, method, fill_bits, out_mem_space, out_data, out_null_mask, out_n_missing);
+} catch (...) { return pandrs::on_exception("pandrs_hip_fill"); }
+
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {
     if (!out_sum || !out_sum_sq || !out_count) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce_moments: bad arguments");

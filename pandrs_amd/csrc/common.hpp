@@ -381,6 +381,9 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
 // rank.hip: the ascending 1-based rank of every row (method = pandrs_hip_rank_method), NaN for NaN and null cells
 int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method,
                    int32_t out_mem_space, double *out);
+// fill.hip: missing cells (null bit, or NaN for F64) repaired in row order (method = pandrs_hip_fill_method)
+int32_t fill_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method, uint64_t fill_bits,
+                   int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_missing);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

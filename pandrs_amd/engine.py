@@ -832,3 +832,64 @@ class Context:
         if st:
             _raise(st)
         return out[:n]
+
+    # -- fill (valid bits, a carry across tiles, a nearby gather) ------------------------------------------------------
+    def fill(self, col, n_rows, method, value=None, out=None, out_mask=None, out_device=None):
+        """Missing cells of one I64 / F64 column repaired on the device (pandrs_hip_fill; PandasCompatExt::fillna /
+        fillna_method / interpolate / ffill / bfill, src/dataframe/pandas_compat/functions.rs:789-918, :3626-3683).  A cell is
+        missing when its null bit is set or, for F64, when it is NaN.  `col` is a (data, mask, dtype) triple on the host or
+        the device, or a ResidentColumn; method is L.FILL_FFILL / BFILL / LINEAR / VALUE.  `value` (VALUE only): an int that
+        fits int64 for an I64 column, a float for F64 (NaN leaves the rows missing).  `out` / `out_mask`: a numpy array or
+        torch CUDA tensor (both in the same space) of at least n_rows cells of the result's dtype / ceil(n_rows / 8) uint8
+        to write into.  -> (values, mask, n_missing): values is int64, or float64 for an F64 column and under LINEAR; mask
+        is the uint8 null bitmap of the rows still missing, None when n_missing == 0.  Both are `out` / `out_mask` when
+        given; else torch tensors on this context's device for device / resident columns (or out_device=True), else
+        numpy arrays."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n, method = int(n_rows), int(method)
+        is_i64 = cc[0].dtype == L.I64
+        out_i64 = is_i64 and method != L.FILL_LINEAR
+        fill_bits = 0
+        if method == L.FILL_VALUE:
+            if is_i64:
+                if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not -(1 << 63) <= int(value) < (1 << 63):
+                    raise ValueError("an I64 column is filled with an int that fits int64, got %r" % (value,))
+                fill_bits = int(value) & 0xFFFFFFFFFFFFFFFF
+            else:
+                if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+                    raise ValueError("an F64 column is filled with a float, got %r" % (value,))
+                fill_bits = int(np.float64(value).view(np.uint64))
+        elif value is not None:
+            raise ValueError("value goes with FILL_VALUE only")
+        nbytes = (n + 7) // 8
+        given = [b for b in (out, out_mask) if b is not None]
+        if given:
+            if len({_is_torch(b) for b in given}) != 1:
+                raise ValueError("out and out_mask must both be numpy arrays or both CUDA tensors")
+            out_device = _is_torch(given[0])
+        elif out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            want, want_mask = (torch.int64 if out_i64 else torch.float64), torch.uint8
+            good = lambda b, dt, k: b.dtype == dt and b.is_contiguous() and b.is_cuda and b.numel() >= k  # noqa: E731
+            make = lambda dt, k: torch.empty(max(k, 1), dtype=dt, device="cuda:%d" % self.device)        # noqa: E731
+        else:
+            want, want_mask = (np.int64 if out_i64 else np.float64), np.uint8
+            good = lambda b, dt, k: isinstance(b, np.ndarray) and b.dtype == dt and b.flags.c_contiguous and b.size >= k  # noqa: E731
+            make = lambda dt, k: np.empty(k, dt)                                                                       # noqa: E731
+        if out is not None and not good(out, want, n):
+            raise ValueError("out must be a contiguous %s numpy array or CUDA tensor of at least n_rows elements" % ("int64" if out_i64 else "float64"))
+        if out_mask is not None and not good(out_mask, want_mask, nbytes):
+            raise ValueError("out_mask must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
+        if given and out_device:
+            self._wait_for_producer()
+        out = make(want, n) if out is None else out
+        out_mask = make(want_mask, nbytes) if out_mask is None else out_mask
+        missing = C.c_int64(0)
+        st = self.lib.pandrs_hip_fill(self.h, sp, cc, n, method, C.c_uint64(fill_bits), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                      _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(missing))
+        if st:
+            _raise(st)
+        return out[:n], (out_mask[:nbytes] if missing.value else None), missing.value

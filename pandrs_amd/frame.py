@@ -685,6 +685,57 @@ class OptimizedDataFrame:
             return np.empty(0, np.float64)
         return np.asarray(get_context().rank(col.view(), col.len(), int(method), out_device=False), dtype=np.float64)
 
+    # -- missing values (dataframe/pandas_compat/functions.rs:789-918, :3626-3683) ------------------------------
+    def _fill(self, column_name, method, value=None):
+        """One pandrs_hip_fill call -> a NEW frame: the named column replaced (same name, same position; Float64 after
+        interpolate; a null mask only when rows are still missing), the other columns shared unchanged.  A cell is
+        missing when its null bit is set or, for Float64, when it is NaN.  Errors before any device call:
+        ColumnNotFound, ColumnTypeMismatch for a String or Boolean column (as describe and rank).  Deviations
+        (pandrs_hip.h): the reference casts every numeric column to f64 and knows no null mask here; Int64 stays Int64
+        under ffill / bfill / fillna."""
+        col = self.column(column_name)
+        if col.dtype not in (L.I64, L.F64):
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a numeric type" % column_name)
+        if col.len() == 0:
+            new = col
+        else:
+            values, mask, _ = get_context().fill(col.view(), col.len(), method, value, out_device=False)
+            new = (Int64Column if values.dtype == np.int64 else Float64Column)(values)
+            new.null_mask = mask
+        result = OptimizedDataFrame()
+        for name in self.column_names:
+            result.add_column(name, new if name == column_name else self.column(name))
+        return result
+
+    def ffill(self, column_name):
+        """ffill (functions.rs:3626-3653): every missing row takes the cell of the last valid row before it; rows in
+        front of the first valid row stay missing."""
+        return self._fill(column_name, L.FILL_FFILL)
+
+    def bfill(self, column_name):
+        """bfill (functions.rs:3655-3683): every missing row takes the cell of the next valid row after it; rows behind
+        the last valid row stay missing."""
+        return self._fill(column_name, L.FILL_BFILL)
+
+    def fillna_method(self, column_name, method):
+        """fillna_method (functions.rs:811-868): "ffill" | "forward" | "bfill" | "backward"."""
+        self.column(column_name)
+        if method in ("ffill", "forward"):
+            return self.ffill(column_name)
+        if method in ("bfill", "backward"):
+            return self.bfill(column_name)
+        raise InvalidValue("Invalid fill method: '%s'. Use 'ffill' or 'bfill'." % (method,))        # functions.rs:846-851
+
+    def interpolate(self, column_name):
+        """interpolate (functions.rs:870-918): a missing row between the valid rows p < i < q becomes
+        a + ((b - a) * (i - p)) / (q - p); rows outside the first and last valid row stay missing.  Float64 always."""
+        return self._fill(column_name, L.FILL_LINEAR)
+
+    def fillna(self, column_name, value):
+        """fillna (functions.rs:789-809): every missing row becomes `value` (an int for an Int64 column, a float for
+        Float64; NaN leaves the rows missing, as in the reference)."""
+        return self._fill(column_name, L.FILL_VALUE, value)
+
     # -- joins (join.rs:32-73) -----------------------------------------------------------------------------
     def inner_join(self, other, left_on, right_on):
         return self._join_impl(other, left_on, right_on, JoinType.Inner)
