@@ -209,6 +209,8 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *   "agg_ablate"        experiments only: switch parts of the lean aggregate off (see experiments/agg2_ablate.py)
  *   "sort_digit_bits"   experiments only: widest radix digit of pandrs_hip_sort_indices, 4 ... 8 (0 = the default, 8;
  *                       experiments/sort_bench.py --digit-bits)
+ *   "topk_path"         tests / experiments: 1 = pandrs_hip_topk always sorts the whole column, -1 = it always selects; 0 = the
+ *                       default, by topk_cutover (experiments/topk_bench.py)
  *   "no_runs"           1 = never the clustered-rows (RUNS) instantiation
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
  *   "test_throw"        tests of the exception firewall (ctx may be NULL): 1 = the entry point's host code throws std::bad_alloc
@@ -687,7 +689,8 @@ int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
  * 64 bits; staging: the host column and a host out.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
  * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
  * col / out, a method outside 0 .. 4 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written.
- * Out of scope: a descending order, pct, a grouped rank, nlargest / nsmallest, rank through the legacy string frame, and
+ * Out of scope: a descending order, pct, a grouped rank, rank through the legacy string frame (nlargest / nsmallest are
+ * pandrs_hip_topk, below), and
  * OptimizedDataFrame::mann_whitney_u (split_dataframe/stats.rs:332: its ties are a chained |a - b| < EPSILON, not equality, and
  * its p-value is an approximation of the reference's own). */
 typedef enum pandrs_hip_rank_method {   /* RankMethod, types.rs:48-59, same order */
@@ -751,6 +754,66 @@ typedef enum pandrs_hip_fill_method {
 int32_t pandrs_hip_fill(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                         int32_t method, uint64_t fill_bits, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,
                         int64_t *out_n_missing);
+
+/* ---- the first k rows of one numeric column in order: nlargest / nsmallest, idxmax / idxmin ----------------------------------
+ * PandasCompatExt::nlargest / nsmallest (src/dataframe/pandas_compat/functions.rs:159-174) and idxmax / idxmin (:175-192); known
+ * answers functions.rs:4369-4391.  One column, I64 or F64, with or without a null mask, n_rows rows, a direction and k >= 0.
+ * The order O(direction) over ALL rows:
+ *   1. the numbers by value, descending for LARGEST, ascending for SMALLEST: F64 by numeric comparison (-0.0 ties 0.0, as in
+ *      pandrs_hip_sort_indices), I64 as integers, exactly;
+ *   2. ties in ascending row order (the reference's sort_by is stable);
+ *   3. then the NaN rows in ascending row order;  4. then the null rows in ascending row order.
+ * NaN and null come last in BOTH directions.  pandrs_hip_topk writes the first min(k, n_rows) rows of O as int64 row indices to
+ * out_rows (out_mem_space), *out_count = min(k, n_rows) and *out_n_numbers = how many of them are numbers: the numbers come
+ * first, so a caller that drops the missing tail (pandas) cuts there.  As a property: out_rows equals the first k entries of
+ * pandrs_hip_sort_indices on that one key with ascending = [direction == SMALLEST], index for index.
+ * pandrs_hip_arg_extreme is idxmin and idxmax in one pass: out_rows[0] = the FIRST row that holds the minimum (Iterator::min_by
+ * keeps the first of equals), out_rows[1] = the LAST row that holds the maximum (max_by keeps the last); NaN and null cells
+ * are skipped; *out_found = 0 when the column holds no number (the reference's None for an empty column; out_rows untouched), else
+ * 1.  The same ties: -0.0 equals 0.0, I64 as integers.
+ * How (topk.hip): (1) one census stream gives the counts of numbers (m), NaN and null cells and the extreme order-preserving
+ * codes with their rows (that is arg_extreme's whole kernel); the output is kn = min(k, m) numbers, then NaN rows, then null
+ * rows; (2) a single-rank most-significant-digit radix select of rank kn - 1 over code - min (LARGEST: max - code), one stream
+ * per 8-bit digit that varies, finds the threshold; kn == m needs none; (3) reduce-then-scan compaction: the rows better than
+ * the threshold, equal to it, NaN and null are counted per tile, one workgroup scans the counts, and a last stream (tiles with
+ * nothing to give are skipped) writes the s better rows to a candidate list, the first kn - s equal rows, NaN rows and null rows
+ * to their final slots, all in row order by wave ballots; (4) s comes back to the host (ONE read-back of its own, 8 bytes of
+ * state that size the next step; the nested sort then makes its own two), pandrs_hip_sort_indices' stable sort orders the s < k candidates and their row numbers are
+ * gathered into out_rows[0, s).  Every hand-off between workgroups is a kernel boundary; no workgroup waits for another.
+ * Geometry (tests read it): topk_tile_rows = 2048 rows per workgroup iteration, topk_blocks_per_cu = 4, grid =
+ * min(topk_blocks_per_cu x compute units, ceil(n_rows / topk_tile_rows)) workgroups striding over the tiles.  Cut-over: from
+ * topk_cutover = 1 / 5 on, i.e. when 5 * min(k, n_rows) >= 1 * n_rows, the column is sorted whole and the first k entries kept: the
+ * earliest measured crossing of select and sort (a narrow-coded column at 100 M rows, docs/EXPERIMENT_LOG.md "Top-k"), rounded
+ * towards the sort.  Both sides give the same output ("topk_path" forces either).
+ * Deviations:
+ *  - NaN: the reference's `partial_cmp(..).unwrap_or(Equal)` is no total order once a NaN cell is present, so its result is
+ *    unspecified.  Here NaN rows are simply last, before the null rows, and arg_extreme skips them.
+ *  - null: the reference reads a missing value as an error or as a number, depending on the frame; here a null row is last and the
+ *    cell under its bit is never looked at.
+ *  - I64: the reference casts to f64, which ties neighbours beyond 2^53; here I64 cells are compared as integers: the position
+ *    pandrs_hip_rank and pandrs_hip_describe take.
+ * Host columns are staged; device and resident columns are read in place (data and out_rows 8-byte aligned, 16 is not needed; a
+ * null mask at any byte offset, bits past n_rows ignored).  out_rows receives exactly min(k, n_rows) entries and nothing beyond.
+ * out_count, out_n_numbers, out_found and arg_extreme's out_rows are host pointers.  pandrs_hip_get_timings: the census and the
+ * select are PANDRS_HIP_PHASE_OTHER, the compaction PANDRS_HIP_PHASE_SCATTER, the sort its own phases; n_partitions = the digit
+ * streams of the select (above the cut-over: the sort's passes).
+ * Workspace, sized up front: 56 bytes per workgroup, 256 digit counts, 32 bytes per topk_tile_rows rows (per-tile counts and
+ * offsets of the four classes), 16 x min(k, n_rows) bytes of candidates, plus pandrs_hip_sort_indices' need for min(k, n_rows)
+ * rows of one key with its permutation (32 bytes per row): 48 bytes per requested row and 1 / 64 byte per column row.  Above the
+ * cut-over: the sort's 24 bytes per row (plus 8 for a code beyond 64 bits) and the permutation's 8.  arg_extreme: the 56 bytes per
+ * workgroup.  Staging: the host column and a host out_rows.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a column that
+ * is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a NULL col / out pointer, k < 0, a direction outside 0 .. 1 or n_rows >= 2^32:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0 or k == 0: OK, nothing written, both counts 0.
+ * Out of scope: keep= variants, a multi-column nlargest, a grouped top-k, String and Boolean columns, the legacy string frame,
+ * argmax / argmin / pct_rank, and rows beyond 2^32. */
+typedef enum pandrs_hip_topk_direction { PANDRS_HIP_TOPK_LARGEST = 0, PANDRS_HIP_TOPK_SMALLEST = 1 } pandrs_hip_topk_direction;
+
+int32_t pandrs_hip_topk(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int64_t k,
+                        int32_t direction, int32_t out_mem_space, int64_t *out_rows, int64_t *out_count, int64_t *out_n_numbers);
+
+int32_t pandrs_hip_arg_extreme(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                               int64_t out_rows[2], int32_t *out_found);
 
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and

@@ -10,6 +10,7 @@
 //                             rolling / expanding / ewm: src/dataframe/window.rs:13-160 (series/window.rs)
 //                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
 //                             rank: src/dataframe/pandas_compat/functions.rs:193-236
+//                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -30,6 +31,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -348,6 +350,18 @@ public:
         }
         return ranks;
     }
+    // nlargest / nsmallest (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:159-174): the min(n, row_count()) rows with
+    // the largest / smallest values of an Int64 or Float64 column, in that order, ties in row order, from one pandrs_hip_topk
+    // call (a radix select, a compaction, a sort of fewer than n rows) - sort_by's first n rows without the sort.  The frame is
+    // assembled as sort_by_columns assembles its own: nulls become 0 / 0.0 / "" / false, no masks, no columns when there are no
+    // rows.  Errors before any device call: ColumnNotFound, Type (a String or Boolean column).  NaN rows, then null rows, come
+    // after every number in both directions; Int64 cells are compared as integers (pandrs_hip.h).
+    OptimizedDataFrame nlargest(size_t n, const std::string &column_name) const { return topk(n, column_name, PANDRS_HIP_TOPK_LARGEST); }
+    OptimizedDataFrame nsmallest(size_t n, const std::string &column_name) const { return topk(n, column_name, PANDRS_HIP_TOPK_SMALLEST); }
+    // idxmax / idxmin (functions.rs:175-192): the LAST row of the largest value (Iterator::max_by) / the FIRST row of the smallest
+    // (min_by), NaN and null cells skipped; nullopt when the column holds no number.  One pandrs_hip_arg_extreme pass for both.
+    std::optional<size_t> idxmax(const std::string &column_name) const { return arg_extreme(column_name, 1); }
+    std::optional<size_t> idxmin(const std::string &column_name) const { return arg_extreme(column_name, 0); }
     // ffill / bfill / fillna_method / interpolate / fillna (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:789-918,
     // :3626-3683): a NEW frame from one pandrs_hip_fill call, the named column replaced (same name, same position; Float64
     // after interpolate; a null mask only when rows are still missing), the other columns copied as they are.  A cell is
@@ -512,6 +526,33 @@ private:
     size_t row_count_ = 0;
     std::shared_ptr<detail::ResidentSet> resident_;
 
+    // one pandrs_hip_topk call (direction = pandrs_hip_topk_direction) -> the frame of those rows, in that order
+    OptimizedDataFrame topk(size_t n, const std::string &column_name, int32_t direction) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        OptimizedDataFrame out;
+        if (row_count_ == 0 || n == 0) return out;
+        const pandrs_hip_column v = view_of(column_name);
+        std::vector<int64_t> idx(std::min(n, row_count_));
+        int64_t count = 0, numbers = 0;
+        detail::check(pandrs_hip_topk(detail::context(), mem_space(), &v, (int64_t)row_count_, (int64_t)idx.size(), direction,
+                                      PANDRS_HIP_MEM_HOST, idx.data(), &count, &numbers));
+        idx.resize((size_t)count);
+        for (size_t i = 0; i < columns.size(); i++) out.add_column(column_names[i], gather(columns[i], idx));
+        return out;
+    }
+    std::optional<size_t> arg_extreme(const std::string &column_name, int which) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        int64_t rows[2] = {0, 0};
+        int32_t found = 0;
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_arg_extreme(detail::context(), mem_space(), &v, (int64_t)row_count_, rows, &found));
+        }
+        if (!found) return std::nullopt;
+        return (size_t)rows[which];
+    }
     // one pandrs_hip_fill call (method = pandrs_hip_fill_method) -> the frame with the named column replaced
     OptimizedDataFrame fill(const std::string &column_name, int32_t method, uint64_t fill_bits) const {
         const Column &c = column(column_name);

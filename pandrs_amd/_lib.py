@@ -24,6 +24,7 @@ WINDOW_KIND_ROLLING, WINDOW_KIND_EXPANDING, WINDOW_KIND_EWM = range(3)
 WINDOW_SUM, WINDOW_MEAN, WINDOW_VAR, WINDOW_STD, WINDOW_MIN, WINDOW_MAX, WINDOW_COUNT = range(7)
 RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_FIRST, RANK_DENSE = range(5)
 FILL_FFILL, FILL_BFILL, FILL_LINEAR, FILL_VALUE = range(4)
+TOPK_LARGEST, TOPK_SMALLEST = range(2)
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -154,6 +155,9 @@ SYMBOLS = {
     "pandrs_hip_rank": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, _P]),
     "pandrs_hip_fill": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_uint64, C.c_int32, _P, _P,
                                     C.POINTER(C.c_int64)]),
+    "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

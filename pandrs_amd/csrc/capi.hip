@@ -98,7 +98,7 @@ int32_t pandrs_hip_ctx_destroy(pandrs_hip_ctx *c) try {
     if (!c) return PANDRS_HIP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release();
+    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release(); c->topk.release();
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) { (void)hipEventDestroy(c->ev_begin[i]); (void)hipEventDestroy(c->ev_end[i]); }
     (void)hipEventDestroy(c->ev_call_begin); (void)hipEventDestroy(c->ev_call_end);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -247,6 +247,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "agg_ablate")) c->opt.agg_ablate = value;
     else if (!std::strcmp(name, "sort_digit_bits")) c->opt.sort_digit_bits = value;
     else if (!std::strcmp(name, "agg_depth")) c->opt.agg_depth = value;
+    else if (!std::strcmp(name, "topk_path")) c->opt.topk_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
 } catch (...) { return pandrs::on_exception("pandrs_hip_ctx_set_option"); }
@@ -511,6 +512,20 @@ int32_t pandrs_hip_fill(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::fill_entry(ctx, mem_space, col, n_rows, method, fill_bits, out_mem_space, out_data, out_null_mask, out_n_missing);
 } catch (...) { return pandrs::on_exception("pandrs_hip_fill"); }
+
+int32_t pandrs_hip_topk(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int64_t k,
+                        int32_t direction, int32_t out_mem_space, int64_t *out_rows, int64_t *out_count, int64_t *out_n_numbers) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "topk: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::topk_entry(ctx, mem_space, col, n_rows, k, direction, out_mem_space, out_rows, out_count, out_n_numbers);
+} catch (...) { return pandrs::on_exception("pandrs_hip_topk"); }
+
+int32_t pandrs_hip_arg_extreme(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                               int64_t out_rows[2], int32_t *out_found) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "arg_extreme: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::arg_extreme_entry(ctx, mem_space, col, n_rows, out_rows, out_found);
+} catch (...) { return pandrs::on_exception("pandrs_hip_arg_extreme"); }
 
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {

@@ -231,6 +231,7 @@ struct Options {
     int64_t agg_v1 = 0;              // 1 = never use the lean persistent aggregate kernel (aggregate2.hip)
     int64_t agg_depth = 0;           // experiments: register-ring depth of aggregate2 (C2 profile)
     int64_t sort_digit_bits = 0;     // experiments: widest radix digit of pandrs_hip_sort_indices (0 = default, 4 ... 8)
+    int64_t topk_path = 0;           // tests / experiments: 1 = pandrs_hip_topk always sorts the column, -1 = it always selects (0 = by the cut-over)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
 
@@ -247,6 +248,7 @@ struct pandrs_hip_ctx {
     pandrs::Arena work, result, staging, temp, result2, result3, side, super, packed, pairs, groups, shuf, absorb, overflow;
     pandrs::Arena filt;          // the retained filter selection (filter.hip)
     pandrs::Arena win;           // window workspace: van Herk prefix / suffix rows, tile and thread scan states (window.hip)
+    pandrs::Arena topk;          // top-k workspace that outlives the nested sort of the candidates: census, tile counts, candidates (topk.hip)
     pandrs::Options opt;
     pandrs_hip_timings timings{};
     pandrs::GroupbyResult gb, gb2, gb3;   // gb2 / gb3: nested results (slice merges, two-level sub-runs)
@@ -384,6 +386,12 @@ int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column
 // fill.hip: missing cells (null bit, or NaN for F64) repaired in row order (method = pandrs_hip_fill_method)
 int32_t fill_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method, uint64_t fill_bits,
                    int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_missing);
+// topk.hip: the first min(k, n_rows) rows in descending / ascending order (direction = pandrs_hip_topk_direction), NaN then null rows last;
+// the first row of the minimum and the last row of the maximum
+int32_t topk_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int64_t k, int32_t direction,
+                   int32_t out_mem_space, int64_t *out_rows, int64_t *out_count, int64_t *out_n_numbers);
+int32_t arg_extreme_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int64_t *out_rows,
+                          int32_t *out_found);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

@@ -198,6 +198,9 @@ size_t engine_workspace_bytes(int64_t n_rows, int n_cols8, int n_cols1);
 // sort, the permutation and extra_work more bytes; the caller takes its own buffers from c->work after the call.
 int32_t sort_order_device(pandrs_hip_ctx *c, const KeyDesc *keys, int32_t n_keys, const int32_t *ascending, const uint32_t *d_rank,
                           int64_t n_codes, int64_t n_rows, int64_t *d_out, size_t extra_work, int64_t **perm_out);
+// c->work bytes the sort itself takes for n_rows rows whose concatenated code has W 64-bit words, without the permutation
+// (8 bytes per row when d_out == nullptr) and extra_work: what sort_order_device asks for, for callers that size up front
+size_t sort_order_workspace(const pandrs_hip_ctx *c, int64_t n_rows, uint32_t W);
 
 // segsort.hip: sorts every partition [0, n_parts) of (keys, payload) ascending by (key, payload),
 // in place, whatever the partition sizes.  `enc`: 0 = payload compared as is, 1 = f64 bits and

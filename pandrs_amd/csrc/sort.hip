@@ -297,6 +297,18 @@ struct SortDigit { uint32_t word, shift, dbits; };
 // the timings and staged what was on the host.  d_out != nullptr: the permutation is written there (pandrs_hip_sort_indices).
 // d_out == nullptr: *perm_out = n_rows int64 taken from c->work, which is then sized for the sort plus extra_work bytes: the
 // caller takes its own buffers from c->work after the call (rank.hip).
+static uint32_t sort_grid(const pandrs_hip_ctx *c, int64_t n_rows) {
+    return (uint32_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * SORT_BLOCKS_PER_CU, (n_rows + SORT_TILE - 1) / SORT_TILE));
+}
+
+// codes [W][S] | second key buffer | two row buffers | counts | offsets | scan | and/or
+size_t sort_order_workspace(const pandrs_hip_ctx *c, int64_t n_rows, uint32_t W) {
+    const size_t n = (size_t)n_rows, n_counts = (size_t)SORT_MAX_BUCKETS * sort_grid(c, n_rows);
+    const size_t S = (n + 31) & ~size_t(31);            // word stride in rows (whole 256-byte pieces)
+    return Arena::padded((size_t)W * S * 8) + Arena::padded(n * 8) + 2 * Arena::padded(n * 4) + 2 * Arena::padded(n_counts * 4 + 4) +
+           Arena::padded(scan_seg_count(n_counts) * 4) + Arena::padded((size_t)W * 16) + 4096;
+}
+
 int32_t sort_order_device(pandrs_hip_ctx *c, const KeyDesc *keys, int32_t n_keys, const int32_t *ascending, const uint32_t *d_rank,
                           int64_t n_codes, int64_t n_rows, int64_t *d_out, size_t extra_work, int64_t **perm_out) {
     const size_t n = (size_t)n_rows;
@@ -358,15 +370,12 @@ int32_t sort_order_device(pandrs_hip_ctx *c, const KeyDesc *keys, int32_t n_keys
         HIP_TRY(hipGetLastError());
     } else {
         // ---- workspace, sized up front: codes [W][S] | second key buffer | two row buffers | counts | offsets | scan | and/or ----
-        const uint32_t G = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * SORT_BLOCKS_PER_CU,
-                                                                           (n_rows + SORT_TILE - 1) / SORT_TILE));
+        const uint32_t G = sort_grid(c, n_rows);
         const int64_t tiles = (n_rows + SORT_TILE - 1) / SORT_TILE;
         const int64_t rows_per_block = ((tiles + G - 1) / G) * SORT_TILE;
         const size_t n_counts = (size_t)SORT_MAX_BUCKETS * G;
         const size_t S = (n + 31) & ~size_t(31);            // word stride in rows (whole 256-byte pieces)
-        ST_TRY(c->work.ensure(Arena::padded((size_t)W * S * 8) + Arena::padded(n * 8) + 2 * Arena::padded(n * 4) +
-                              2 * Arena::padded(n_counts * 4 + 4) + Arena::padded(scan_seg_count(n_counts) * 4) +
-                              Arena::padded((size_t)W * 16) + 4096 + own_work, c->stream));
+        ST_TRY(c->work.ensure(sort_order_workspace(c, n_rows, W) + own_work, c->stream));
         if (!d_out && !(d_out = c->work.take<int64_t>(n))) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (sort)");
         uint64_t *words = c->work.take<uint64_t>((size_t)W * S);
         uint64_t *kbuf = c->work.take<uint64_t>(n);

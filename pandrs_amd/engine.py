@@ -893,3 +893,55 @@ class Context:
         if st:
             _raise(st)
         return out[:n], (out_mask[:nbytes] if missing.value else None), missing.value
+
+    # -- top-k (radix select, compaction, a sort of fewer than k rows) ---------------------------------------------------
+    def topk(self, col, n_rows, k, largest=True, out=None, out_device=None):
+        """The first min(k, n_rows) rows of one I64 / F64 column in descending (largest) or ascending order on the device
+        (pandrs_hip_topk; PandasCompatExt::nlargest / nsmallest, src/dataframe/pandas_compat/functions.rs:159-174): numbers
+        by value, ties in row order, then the NaN rows, then the null rows - the first k entries of sort_indices on that
+        key.  `col` is a (data, mask, dtype) triple on the host or the device, or a ResidentColumn.  `out`: an int64 numpy
+        array or torch CUDA tensor of at least min(k, n_rows) elements to write into.  -> (rows, n_numbers): the int64 row
+        indices (`out` when given; else a torch tensor on this context's device for device / resident columns or
+        out_device=True, else a numpy array) and how many of them hold a number (they come first)."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n, k = int(n_rows), int(k)
+        kk = max(0, min(k, n))
+        if out is not None:
+            out_device = _is_torch(out)
+            if out_device:
+                import torch
+                ok = out.dtype == torch.int64 and out.is_contiguous() and out.is_cuda and out.numel() >= kk
+            else:
+                ok = isinstance(out, np.ndarray) and out.dtype == np.int64 and out.flags.c_contiguous and out.size >= kk
+            if not ok:
+                raise ValueError("out must be a contiguous int64 numpy array or CUDA tensor of at least min(k, n_rows) elements")
+            if out_device:
+                self._wait_for_producer()
+        else:
+            if out_device is None:
+                out_device = sp == L.MEM_DEVICE
+            if out_device:
+                import torch
+                out = torch.empty(max(kk, 1), dtype=torch.int64, device="cuda:%d" % self.device)
+            else:
+                out = np.empty(kk, np.int64)
+        cnt, num = C.c_int64(0), C.c_int64(0)
+        st = self.lib.pandrs_hip_topk(self.h, sp, cc, n, k, L.TOPK_LARGEST if largest else L.TOPK_SMALLEST,
+                                      L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if kk else None, C.byref(cnt), C.byref(num))
+        if st:
+            _raise(st)
+        return out[:cnt.value], num.value
+
+    def arg_extreme(self, col, n_rows):
+        """idxmin and idxmax of one I64 / F64 column in one pass on the device (pandrs_hip_arg_extreme; functions.rs:175-192):
+        -> (the FIRST row that holds the minimum, the LAST row that holds the maximum), NaN and null cells skipped; None when
+        the column holds no number.  `col` as in topk."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        rows = (C.c_int64 * 2)(-1, -1)
+        found = C.c_int32(0)
+        st = self.lib.pandrs_hip_arg_extreme(self.h, sp, cc, int(n_rows), rows, C.byref(found))
+        if st:
+            _raise(st)
+        return (int(rows[0]), int(rows[1])) if found.value else None

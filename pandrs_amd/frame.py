@@ -685,6 +685,60 @@ class OptimizedDataFrame:
             return np.empty(0, np.float64)
         return np.asarray(get_context().rank(col.view(), col.len(), int(method), out_device=False), dtype=np.float64)
 
+    # -- nlargest / nsmallest / idxmax / idxmin (dataframe/pandas_compat/functions.rs:159-192) --------------------
+    def _numeric(self, column_name):
+        col = self.column(column_name)
+        if col.dtype not in (L.I64, L.F64):
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a numeric type" % column_name)
+        return col
+
+    def _topk(self, n, column_name, largest):
+        """One pandrs_hip_topk call -> the frame of those rows, assembled as sort_by_columns assembles its own
+        (select_rows_by_indices: nulls become 0 / 0.0 / "" / false, no masks, no columns when there are no rows)."""
+        col = self._numeric(column_name)
+        n = int(n)
+        if n < 0:
+            raise InvalidValue("n must not be negative, got %d" % n)
+        result = OptimizedDataFrame()
+        if self._row_count == 0 or n == 0:
+            return result
+        ctx = get_context()
+        idx, _ = ctx.topk(col.view(), self._row_count, n, largest, out_device=True)
+        g = _Gatherer(ctx, idx, idx)
+        for name in self.column_names:
+            result.add_column(name, g.take(self.column(name), left=True))
+        return result
+
+    def nlargest(self, n, column):
+        """PandasCompatExt::nlargest (functions.rs:159-166): the min(n, row_count()) rows with the largest values of an
+        Int64 or Float64 column, largest first, ties in row order, from one device call (pandrs_hip_topk: a radix select,
+        a compaction, a sort of fewer than n rows) - sort_by(column, False)'s first n rows without the sort.  Errors before
+        any device call: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column (as rank).  Deviations
+        (pandrs_hip.h): NaN rows, then null rows, come after every number (the reference's order with a NaN present is
+        unspecified); Int64 cells are compared as integers."""
+        return self._topk(n, column, True)
+
+    def nsmallest(self, n, column):
+        """PandasCompatExt::nsmallest (functions.rs:167-174): as nlargest, smallest first; NaN and null rows still last."""
+        return self._topk(n, column, False)
+
+    def _idx_extreme(self, column_name, which):
+        col = self._numeric(column_name)
+        if col.len() == 0:
+            return None
+        rows = get_context().arg_extreme(col.view(), col.len())
+        return None if rows is None else rows[which]
+
+    def idxmax(self, column):
+        """PandasCompatExt::idxmax (functions.rs:175-183): the row of the largest value, the LAST one among equals
+        (Iterator::max_by), NaN and null cells skipped; None when the column holds no number.  One device pass."""
+        return self._idx_extreme(column, 1)
+
+    def idxmin(self, column):
+        """PandasCompatExt::idxmin (functions.rs:184-192): the row of the smallest value, the FIRST one among equals
+        (Iterator::min_by), NaN and null cells skipped; None when the column holds no number.  One device pass."""
+        return self._idx_extreme(column, 0)
+
     # -- missing values (dataframe/pandas_compat/functions.rs:789-918, :3626-3683) ------------------------------
     def _fill(self, column_name, method, value=None):
         """One pandrs_hip_fill call -> a NEW frame: the named column replaced (same name, same position; Float64 after
