@@ -211,6 +211,10 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *                       experiments/sort_bench.py --digit-bits)
  *   "topk_path"         tests / experiments: 1 = pandrs_hip_topk always sorts the whole column, -1 = it always selects; 0 = the
  *                       default, by topk_cutover (experiments/topk_bench.py)
+ *   "isin_path"         tests / experiments: 1 = pandrs_hip_isin takes the LDS set wherever the list fits, 2 = it always builds the
+ *                       global set; 0 = the default, by the list's size (isin_lds_max_values; experiments/predicate_bench.py)
+ *   "predicate_path"    tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in its loop; 0 = the
+ *                       default, integers compared against the interval the host bisects (the same bits; experiments/predicate_bench.py)
  *   "no_runs"           1 = never the clustered-rows (RUNS) instantiation
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
  *   "test_throw"        tests of the exception firewall (ctx may be NULL): 1 = the entry point's host code throws std::bad_alloc
@@ -745,7 +749,7 @@ int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
  * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
  * col / out_data, a method outside 0 .. 3 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written,
  * *out_n_missing = 0.
- * Out of scope: limit=, dropna / isna / count_na, non-linear interpolation, group-wise fills, String and Boolean columns, the
+ * Out of scope: limit=, non-linear interpolation (dropna / isna / count_na: pandrs_hip_predicate, below), group-wise fills, String and Boolean columns, the
  * legacy string frame, TimeSeries::fillna_forward. */
 typedef enum pandrs_hip_fill_method {
     PANDRS_HIP_FILL_FFILL = 0, PANDRS_HIP_FILL_BFILL = 1, PANDRS_HIP_FILL_LINEAR = 2, PANDRS_HIP_FILL_VALUE = 3
@@ -814,6 +818,75 @@ int32_t pandrs_hip_topk(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
 
 int32_t pandrs_hip_arg_extreme(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                                int64_t out_rows[2], int32_t *out_found);
+
+/* ---- row masks of one column: compare, between, isna, isin ---------------------------------------------------------------------
+ * PandasCompatExt::gt / ge / lt / le / eq_value / ne_value (src/dataframe/pandas_compat/helpers/comparison_ops.rs:7-46), between
+ * (functions.rs:253-257), is_between (functions.rs:4141-4161), isna / notna (:930-933, :1312-1315), is_finite / is_infinite
+ * (:4016-4024), isin / isin_numeric (functions.rs:141-158); known answers functions.rs:4362-4367, :4405-4410, :5007-5008,
+ * :8121-8131, :8143-8147, :8348-8352, :8520-8524.  What filter / par_filter / select_by_mask consume, built where the column lives.
+ * Output: out_bits is an LSB-first bitmap of ceil(n_rows / 8) bytes, bit = 1 the row is selected: the data of a BOOLBITS column
+ * with no null mask, so pandrs_hip_filter_indices takes it in place.  out_bits may be NULL (the count only); *out_count = the
+ * number of set bits (out_count may be NULL when out_bits is not).  Bits at and beyond n_rows in the last byte are 0; no byte at
+ * or beyond ceil(n_rows / 8) is written (the 64-row words are stored bytewise), and out_bits may have any byte alignment.
+ * pandrs_hip_predicate, col I64 or F64 (any other dtype: PANDRS_HIP_ERR_TYPE_MISMATCH).  The reference goes through
+ * get_column_numeric_values, so every compare happens in f64: an I64 cell is first converted with (double)v (round to nearest
+ * even, Rust's `as f64`), so 2^53 + 1 equals 2^53 under EQ, as in the reference.  With v the cell and a, b the arguments:
+ *   GT / GE / LT / LE   !isnan(v) && v OP a
+ *   EQ                  !isnan(v) && fabs(v - a) < DBL_EPSILON          NE   isnan(v) || fabs(v - a) >= DBL_EPSILON
+ *                       (v = a = +inf: both false, inf - inf is NaN; the subtraction is rounded on its own, no fused operation)
+ *   BETWEEN             a <= v && v <= b (between; is_between inclusive)          BETWEEN_EXCLUSIVE   a < v && v < b
+ *   ISNA / NOTNA / IS_FINITE / IS_INFINITE   f64::is_nan / !is_nan / is_finite / is_infinite
+ * A NaN a or b needs no special case: the expressions answer it.  b is read by the two BETWEEN ops only, a by neither of the last four.
+ * pandrs_hip_isin: the reference compares to_bits() (functions.rs:152-155): -0.0 is not 0.0, and a NaN matches only a NaN with the
+ * same payload.  The key compared, by the dtypes of col and values (any other pairing: PANDRS_HIP_ERR_TYPE_MISMATCH):
+ *   F64 / F64          raw bits
+ *   I64 / F64          the bits of (double)v, as in the reference
+ *   I64 / I64          integers compared as integers (no reference counterpart: for ids beyond 2^53)
+ *   U32CODE / U32CODE  string-pool codes (isin on a String column: the caller maps its strings to codes, unknown strings dropped)
+ * values->null_mask must be NULL (PANDRS_HIP_ERR_INVALID_ARGUMENT); duplicates are allowed; n_values == 0 selects nothing (every
+ * row with negate).  negate != 0 inverts every row's bit.
+ * Deviation: a cell whose null bit is set behaves as NaN under pandrs_hip_predicate and never matches under pandrs_hip_isin (its
+ * bit is 1 with negate); the cell under the bit is not looked at.  The reference fails on a missing value (src/dataframe/base.rs:
+ * 555-561).  The same position as pandrs_hip_fill.
+ * How (predicate.hip): rows in tiles, row p0 + r * 256 + tid, so every load is coalesced and one wave ballot is the 64-row word;
+ * counts are popcounts summed per workgroup, one atomic add each.  Compare: one stream; for F64 the kernel is instantiated per op;
+ * for I64, (double)v never decreases as v grows, so an op selects an interval of integers (NE: the complement of one) whose ends the
+ * host finds by bisection with the very expression above, and the stream compares integers: the same bits, no conversion per row.
+ * isin: an open-addressing set of 64-bit keys, a power-of-two slot count >= 2 x n_values, hashed with the library's key mixer
+ * (integral f64 values differ in high bits only); the empty marker (all ones, also a NaN payload) is never stored: "the marker is
+ * listed" is one flag.  Up to isin_lds_max_values = 4096 values every workgroup builds the set in LDS (at most 64 KiB of table + 64 bytes, two
+ * workgroups per CU) with 64-bit compare-and-swap and probes it per row; beyond, one kernel builds it in the workspace and a second
+ * probes it: the kernel boundary is the only hand-off, no workgroup waits for another, every insert and probe loop is bounded by the
+ * slot count.  "isin_path" forces either; both give the same output.
+ * Geometry (tests read it): predicate_tile_rows = 2048 rows per workgroup iteration, predicate_blocks_per_cu = 4, grid =
+ * min(predicate_blocks_per_cu x compute units, ceil(n_rows / predicate_tile_rows)) workgroups striding over the tiles (an LDS set
+ * beyond 32 KiB: 2 per compute unit).
+ * Buffers: host columns, a host value list and a host out_bits are staged; device and resident columns are read in place.  Column
+ * data and values are 8-byte aligned (4-byte for U32CODE); a null mask at any byte offset, bits past n_rows ignored.  mem_space,
+ * values_mem_space and out_mem_space are independent.  out_count is a host pointer.  pandrs_hip_get_timings: the compare is
+ * PANDRS_HIP_PHASE_AGGREGATE; isin's set is PANDRS_HIP_PHASE_BUILD, its stream PANDRS_HIP_PHASE_PROBE, table_slots the slot count,
+ * n_partitions 1 for the LDS set and 2 for the global one.
+ * Workspace, sized up front: the counter; for the global set 8 bytes per slot (16 to 32 bytes per listed value); staging: a host
+ * column, a host value list and a host out_bits.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL col /
+ * values, out_bits and out_count both NULL, an op outside 0 .. 11, n_rows < 0, n_values < 0, n_values > 2^30 or n_rows >= 2^32:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written, *out_count = 0.
+ * Out of scope: combining two masks (and / or / not), predicates between two columns, string predicates (str_contains and the
+ * like), where_cond / mask / clip, isin through the legacy string frame, the multi-GPU path. */
+typedef enum pandrs_hip_pred_op {
+    PANDRS_HIP_PRED_GT = 0, PANDRS_HIP_PRED_GE = 1, PANDRS_HIP_PRED_LT = 2, PANDRS_HIP_PRED_LE = 3,
+    PANDRS_HIP_PRED_EQ = 4, PANDRS_HIP_PRED_NE = 5,
+    PANDRS_HIP_PRED_BETWEEN = 6,            /* a <= v && v <= b */
+    PANDRS_HIP_PRED_BETWEEN_EXCLUSIVE = 7,  /* a <  v && v <  b */
+    PANDRS_HIP_PRED_ISNA = 8, PANDRS_HIP_PRED_NOTNA = 9, PANDRS_HIP_PRED_IS_FINITE = 10, PANDRS_HIP_PRED_IS_INFINITE = 11
+} pandrs_hip_pred_op;
+
+int32_t pandrs_hip_predicate(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                             int32_t op, double a, double b, int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count);
+
+int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                        int32_t values_mem_space, const pandrs_hip_column *values, int64_t n_values, int32_t negate,
+                        int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count);
 
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and

@@ -11,6 +11,10 @@
 //                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
 //                             rank: src/dataframe/pandas_compat/functions.rs:193-236
 //                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
+//                             gt / ge / lt / le / eq_value / ne_value: pandas_compat/helpers/comparison_ops.rs:7-46;
+//                             between / is_between / isna / notna / is_finite / is_infinite / isin / isin_numeric /
+//                             query_* / dropna / count_na / has_nulls / count_value: functions.rs:141-158, :253-257,
+//                             :920-933, :1312-1315, :2776-2795, :3837-3840, :4016-4024, :4089-4095, :4141-4161, :4187-4190
 //   Column / *Column          src/column/{int64,float64,string,boolean}_column.rs, core/column.rs:163-177
 //   GroupBy, AggregateOp      group/types.rs:11-55, group/aggregation.rs:763-871, group/operations.rs:438-547
 //   LazyFrame                 src/optimized/lazy.rs:98-170, :186-425
@@ -114,6 +118,13 @@ public:
     std::string get(uint32_t code) const {
         std::lock_guard<std::mutex> lock(mu_);
         return strings_.at(code);
+    }
+    // the code of a string the pool already holds; nullopt for one it has never seen (nothing is inserted)
+    std::optional<uint32_t> find(const std::string &s) const {
+        std::lock_guard<std::mutex> lock(mu_);
+        auto it = codes_.find(s);
+        if (it == codes_.end()) return std::nullopt;
+        return it->second;
     }
     // rank[code] = position of the code's string in byte-wise order (Rust String: Ord; std::string compares its
     // chars as unsigned char): the table pandrs_hip_sort_indices orders string keys by
@@ -390,6 +401,51 @@ public:
         }
         return fill(column_name, PANDRS_HIP_FILL_VALUE, bits);
     }
+    // ---- row masks (PandasCompatExt: helpers/comparison_ops.rs:7-46, functions.rs:141-158, :253-257, :4141-4161) ----
+    // gt / ge / lt / le / eq_value / ne_value / between / is_between / isna / notna / is_finite / is_infinite: the reference's
+    // Vec<bool>, from one pandrs_hip_predicate call.  Every compare happens in f64 (an Int64 cell as `v as f64`); a cell under a
+    // null bit behaves as NaN (pandrs_hip.h).  Errors before any device call: ColumnNotFound, Type (a String or Boolean column).
+    std::vector<bool> gt(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_GT, value); }
+    std::vector<bool> ge(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_GE, value); }
+    std::vector<bool> lt(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_LT, value); }
+    std::vector<bool> le(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_LE, value); }
+    std::vector<bool> eq_value(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_EQ, value); }
+    std::vector<bool> ne_value(const std::string &column_name, double value) const { return predicate(column_name, PANDRS_HIP_PRED_NE, value); }
+    std::vector<bool> between(const std::string &column_name, double lower, double upper) const {
+        return predicate(column_name, PANDRS_HIP_PRED_BETWEEN, lower, upper);
+    }
+    std::vector<bool> is_between(const std::string &column_name, double lower, double upper, bool inclusive = true) const {
+        return predicate(column_name, inclusive ? PANDRS_HIP_PRED_BETWEEN : PANDRS_HIP_PRED_BETWEEN_EXCLUSIVE, lower, upper);
+    }
+    std::vector<bool> isna(const std::string &column_name) const { return predicate(column_name, PANDRS_HIP_PRED_ISNA); }
+    std::vector<bool> notna(const std::string &column_name) const { return predicate(column_name, PANDRS_HIP_PRED_NOTNA); }
+    std::vector<bool> is_finite(const std::string &column_name) const { return predicate(column_name, PANDRS_HIP_PRED_IS_FINITE); }
+    std::vector<bool> is_infinite(const std::string &column_name) const { return predicate(column_name, PANDRS_HIP_PRED_IS_INFINITE); }
+    // count_na / has_nulls / count_value (functions.rs:3837-3840, :4187-4190, :4089-4095): the count-only form, no mask is written
+    size_t count_na(const std::string &column_name) const { return predicate_count(column_name, PANDRS_HIP_PRED_ISNA, 0.0); }
+    bool has_nulls(const std::string &column_name) const { return predicate_count(column_name, PANDRS_HIP_PRED_ISNA, 0.0) > 0; }
+    size_t count_value(const std::string &column_name, double value) const { return predicate_count(column_name, PANDRS_HIP_PRED_EQ, value); }
+    // query_gt / query_lt / query_eq / dropna (functions.rs:2776-2795, :920-929): predicate -> filter_indices -> filter_gather,
+    // the frame assembled as filter assembles its own (this mirror keeps the mask in host memory, as it keeps its columns)
+    OptimizedDataFrame query_gt(const std::string &column_name, double value) const { return predicate_rows(column_name, PANDRS_HIP_PRED_GT, value); }
+    OptimizedDataFrame query_lt(const std::string &column_name, double value) const { return predicate_rows(column_name, PANDRS_HIP_PRED_LT, value); }
+    OptimizedDataFrame query_eq(const std::string &column_name, double value) const { return predicate_rows(column_name, PANDRS_HIP_PRED_EQ, value); }
+    OptimizedDataFrame dropna(const std::string &column_name) const { return predicate_rows(column_name, PANDRS_HIP_PRED_NOTNA, 0.0); }
+    // isin_numeric (functions.rs:150-158): the cell's f64 bits are in the list's (-0.0 is not 0.0); a null cell never matches
+    std::vector<bool> isin_numeric(const std::string &column_name, const std::vector<double> &values) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        return isin_call(column_name, pandrs_hip_column{values.data(), nullptr, PANDRS_HIP_F64, 0}, (int64_t)values.size());
+    }
+    // isin (functions.rs:141-149) on a String column, through pool codes; a string the pool has never seen is dropped from the list
+    std::vector<bool> isin(const std::string &column_name, const std::vector<std::string> &values) const {
+        const Column &c = column(column_name);
+        if (c.index() != 2) throw Error(Error::Type, "Column '" + column_name + "' is not a string type");
+        std::vector<uint32_t> codes;
+        for (auto &s : values)
+            if (auto code = StringPool::global().find(s)) codes.push_back(*code);
+        return isin_call(column_name, pandrs_hip_column{codes.data(), nullptr, PANDRS_HIP_U32CODE, 0}, (int64_t)codes.size());
+    }
     // describe_all (stats.rs:157-171): every Int64 / Float64 column; one whose describe fails with InvalidValue is left out
     std::map<std::string, StatDescribe> describe_all() const {
         std::map<std::string, StatDescribe> results;
@@ -575,6 +631,49 @@ private:
             else out.add_column(column_names[k], std::move(of));
         }
         return out;
+    }
+
+    // one pandrs_hip_predicate call (op = pandrs_hip_pred_op) -> the packed mask and its count
+    std::vector<uint8_t> predicate_bits(const std::string &column_name, int32_t op, double a, double b, int64_t *count, bool want_bits) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        std::vector<uint8_t> bits(want_bits ? (row_count_ + 7) / 8 : 0);
+        *count = 0;
+        if (!row_count_) return bits;
+        const pandrs_hip_column v = view_of(column_name);
+        detail::check(pandrs_hip_predicate(detail::context(), mem_space(), &v, (int64_t)row_count_, op, a, b, PANDRS_HIP_MEM_HOST,
+                                           want_bits ? bits.data() : nullptr, count));
+        return bits;
+    }
+    static std::vector<bool> unpack(const std::vector<uint8_t> &bits, size_t n) {
+        std::vector<bool> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = (bits[i >> 3] >> (i & 7)) & 1;
+        return out;
+    }
+    std::vector<bool> predicate(const std::string &column_name, int32_t op, double a = 0.0, double b = 0.0) const {
+        int64_t count = 0;
+        return unpack(predicate_bits(column_name, op, a, b, &count, true), row_count_);
+    }
+    size_t predicate_count(const std::string &column_name, int32_t op, double a) const {
+        int64_t count = 0;
+        predicate_bits(column_name, op, a, 0.0, &count, false);
+        return (size_t)count;
+    }
+    OptimizedDataFrame predicate_rows(const std::string &column_name, int32_t op, double a) const {
+        int64_t count = 0;
+        const std::vector<uint8_t> bits = predicate_bits(column_name, op, a, 0.0, &count, true);
+        if (row_count_ == 0) return empty_columns();
+        return compact(pandrs_hip_column{bits.data(), nullptr, PANDRS_HIP_BOOLBITS, 0}, PANDRS_HIP_MEM_HOST).first;
+    }
+    std::vector<bool> isin_call(const std::string &column_name, const pandrs_hip_column &values, int64_t n_values) const {
+        std::vector<uint8_t> bits((row_count_ + 7) / 8);
+        if (row_count_) {
+            int64_t count = 0;
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_isin(detail::context(), mem_space(), &v, (int64_t)row_count_, PANDRS_HIP_MEM_HOST, &values, n_values, 0,
+                                          PANDRS_HIP_MEM_HOST, bits.data(), &count));
+        }
+        return unpack(bits, row_count_);
     }
 
     void window_column(const std::string &name) const {

@@ -25,6 +25,8 @@ WINDOW_SUM, WINDOW_MEAN, WINDOW_VAR, WINDOW_STD, WINDOW_MIN, WINDOW_MAX, WINDOW_
 RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_FIRST, RANK_DENSE = range(5)
 FILL_FFILL, FILL_BFILL, FILL_LINEAR, FILL_VALUE = range(4)
 TOPK_LARGEST, TOPK_SMALLEST = range(2)
+PRED_GT, PRED_GE, PRED_LT, PRED_LE, PRED_EQ, PRED_NE, PRED_BETWEEN, PRED_BETWEEN_EXCLUSIVE, PRED_ISNA, PRED_NOTNA, PRED_IS_FINITE, \
+    PRED_IS_INFINITE = range(12)
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -158,6 +160,10 @@ SYMBOLS = {
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "pandrs_hip_predicate": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, _P,
+                                         C.POINTER(C.c_int64)]),
+    "pandrs_hip_isin": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32,
+                                    C.c_int32, _P, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -248,6 +248,8 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "sort_digit_bits")) c->opt.sort_digit_bits = value;
     else if (!std::strcmp(name, "agg_depth")) c->opt.agg_depth = value;
     else if (!std::strcmp(name, "topk_path")) c->opt.topk_path = value;
+    else if (!std::strcmp(name, "isin_path")) c->opt.isin_path = value;
+    else if (!std::strcmp(name, "predicate_path")) c->opt.predicate_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
 } catch (...) { return pandrs::on_exception("pandrs_hip_ctx_set_option"); }
@@ -526,6 +528,21 @@ int32_t pandrs_hip_arg_extreme(pandrs_hip_ctx *ctx, int32_t mem_space, const pan
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::arg_extreme_entry(ctx, mem_space, col, n_rows, out_rows, out_found);
 } catch (...) { return pandrs::on_exception("pandrs_hip_arg_extreme"); }
+
+int32_t pandrs_hip_predicate(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, double a,
+                             double b, int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "predicate: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::predicate_entry(ctx, mem_space, col, n_rows, op, a, b, out_mem_space, out_bits, out_count);
+} catch (...) { return pandrs::on_exception("pandrs_hip_predicate"); }
+
+int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t values_mem_space,
+                        const pandrs_hip_column *values, int64_t n_values, int32_t negate, int32_t out_mem_space, uint8_t *out_bits,
+                        int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "isin: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::isin_entry(ctx, mem_space, col, n_rows, values_mem_space, values, n_values, negate, out_mem_space, out_bits, out_count);
+} catch (...) { return pandrs::on_exception("pandrs_hip_isin"); }
 
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {

@@ -232,6 +232,8 @@ struct Options {
     int64_t agg_depth = 0;           // experiments: register-ring depth of aggregate2 (C2 profile)
     int64_t sort_digit_bits = 0;     // experiments: widest radix digit of pandrs_hip_sort_indices (0 = default, 4 ... 8)
     int64_t topk_path = 0;           // tests / experiments: 1 = pandrs_hip_topk always sorts the column, -1 = it always selects (0 = by the cut-over)
+    int64_t isin_path = 0;           // tests / experiments: 1 = pandrs_hip_isin takes the LDS set wherever the list fits, 2 = always the global set (0 = by the list's size)
+    int64_t predicate_path = 0;      // tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in the loop instead of comparing integers against the bisected interval
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
 
@@ -392,6 +394,12 @@ int32_t topk_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column
                    int32_t out_mem_space, int64_t *out_rows, int64_t *out_count, int64_t *out_n_numbers);
 int32_t arg_extreme_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int64_t *out_rows,
                           int32_t *out_found);
+// predicate.hip: one bit per row (1 = selected) of a compare against constants / a membership test, and the count of set bits
+int32_t predicate_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, double a, double b,
+                        int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count);
+int32_t isin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t values_mem_space,
+                   const pandrs_hip_column *values, int64_t n_values, int32_t negate, int32_t out_mem_space, uint8_t *out_bits,
+                   int64_t *out_count);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

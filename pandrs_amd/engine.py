@@ -945,3 +945,73 @@ class Context:
         if st:
             _raise(st)
         return (int(rows[0]), int(rows[1])) if found.value else None
+
+    # -- row masks (a compare stream, a set probe) ------------------------------------------------------------------------
+    def _mask_out(self, n, sp, out, out_device, count_only):
+        """The out_bits buffer of predicate / isin: -> (buffer or None, lives on the device)."""
+        nbytes = (n + 7) // 8
+        if count_only:
+            if out is not None:
+                raise ValueError("count_only takes no out")
+            return None, False
+        if out is not None:
+            out_device = _is_torch(out)
+            if out_device:
+                import torch
+                ok = out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda and out.numel() >= nbytes
+            else:
+                ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= nbytes
+            if not ok:
+                raise ValueError("out must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
+            if out_device:
+                self._wait_for_producer()
+            return out, out_device
+        if out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            return torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda:%d" % self.device), True
+        return np.empty(nbytes, np.uint8), False
+
+    def predicate(self, col, n_rows, op, a=0.0, b=0.0, out=None, out_device=None, count_only=False):
+        """One row mask of one I64 / F64 column on the device (pandrs_hip_predicate; PandasCompatExt::gt / ge / lt / le /
+        eq_value / ne_value / between / is_between / isna / notna / is_finite / is_infinite,
+        src/dataframe/pandas_compat/helpers/comparison_ops.rs:7-46, functions.rs:253-257, :4141-4161).  `col` is a (data, mask,
+        dtype) triple on the host or the device, or a ResidentColumn; op is L.PRED_*; a and b its f64 arguments (b: the two
+        BETWEEN ops).  Every compare happens in f64; a null cell behaves as NaN.  `out`: a uint8 numpy array or torch CUDA
+        tensor of at least ceil(n_rows / 8) elements to write into.  -> (bits, count): the LSB-first bitmap, bit = 1 the row
+        is selected - the data of a BOOLBITS column, which filter_indices takes as (bits, None, L.BOOLBITS) - and the number
+        of set bits.  bits is `out` when given; else a torch tensor on this context's device for device / resident columns
+        (or out_device=True), else a numpy array; None with count_only."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n = int(n_rows)
+        out, out_device = self._mask_out(n, sp, out, out_device, count_only)
+        cnt = C.c_int64(0)
+        st = self.lib.pandrs_hip_predicate(self.h, sp, cc, n, int(op), float(a), float(b), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                           _ptr(out) if n else None, C.byref(cnt))
+        if st:
+            _raise(st)
+        return (None if out is None else out[:(n + 7) // 8]), cnt.value
+
+    def isin(self, col, n_rows, values, negate=False, out=None, out_device=None, count_only=False):
+        """Membership of every cell of one column in a value list on the device (pandrs_hip_isin; PandasCompatExt::isin /
+        isin_numeric, functions.rs:141-158): cells are compared by their bits (-0.0 is not 0.0, a NaN matches the same payload
+        only).  `col` as in predicate, also U32CODE; `values` is a (data, None, dtype) triple on the host or the device (its
+        space is independent of the column's): F64 / F64, I64 / F64 (the cell as f64), I64 / I64 (as integers) or U32CODE /
+        U32CODE.  A null cell never matches; `negate` inverts every bit.  -> (bits, count) as predicate."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        vdata, vmask, vdt = tuple(values)
+        if vmask is not None:
+            raise ValueError("the value list takes no null mask")
+        n_values = int(vdata.numel() if _is_torch(vdata) else np.asarray(vdata).shape[0])
+        vc, vsp = self._cols([(vdata, None, vdt)], keep)
+        n = int(n_rows)
+        out, out_device = self._mask_out(n, sp, out, out_device, count_only)
+        cnt = C.c_int64(0)
+        st = self.lib.pandrs_hip_isin(self.h, sp, cc, n, vsp, vc, n_values, 1 if negate else 0, L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                      _ptr(out) if n else None, C.byref(cnt))
+        if st:
+            _raise(st)
+        return (None if out is None else out[:(n + 7) // 8]), cnt.value

@@ -118,6 +118,10 @@ class StringPool:
     def get(self, code):
         return self._strings[code]
 
+    def find(self, s):
+        """The code of a string the pool already holds, None for one it has never seen (nothing is inserted)."""
+        return self._code.get(s)
+
     def rank_table(self):
         """rank[code] = position of the code's string in byte-wise order (Rust String: Ord).  UTF-8 byte order and
         code-point order (Python str comparison) are the same order."""
@@ -789,6 +793,131 @@ class OptimizedDataFrame:
         """fillna (functions.rs:789-809): every missing row becomes `value` (an int for an Int64 column, a float for
         Float64; NaN leaves the rows missing, as in the reference)."""
         return self._fill(column_name, L.FILL_VALUE, value)
+
+    # -- row masks (dataframe/pandas_compat/helpers/comparison_ops.rs:7-46, functions.rs:141-158, :253-257, :4141-4161) ----
+    def _predicate(self, column_name, op, a=0.0, b=0.0):
+        """One pandrs_hip_predicate call -> the reference's Vec<bool> as a list of bool.  Every compare happens in f64 (an
+        Int64 cell as `v as f64`); a cell under a null bit behaves as NaN (pandrs_hip.h: the reference fails on a missing
+        value).  Errors before any device call: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column."""
+        col = self._numeric(column_name)
+        if col.len() == 0:
+            return []
+        bits, _ = get_context().predicate(col.view(), col.len(), op, a, b, out_device=False)
+        return np.unpackbits(bits, count=col.len(), bitorder="little").astype(bool).tolist()
+
+    def _predicate_count(self, column_name, op, a=0.0):
+        col = self._numeric(column_name)
+        if col.len() == 0:
+            return 0
+        return get_context().predicate(col.view(), col.len(), op, a, count_only=True)[1]
+
+    def _predicate_rows(self, column_name, op, a=0.0):
+        """predicate -> filter_indices on the device mask -> filter_gather per column: the mask does not visit the host.
+        The result is filter's (nulls become 0 / 0.0 / "" / false, no masks; no selected row: every column with 0 rows)."""
+        col = self._numeric(column_name)
+        if self._row_count == 0:
+            return self._empty_columns()
+        bits, _ = get_context().predicate(col.view(), self._row_count, op, a, out_device=True)
+        return self._compact((bits, None, L.BOOLBITS))[0]
+
+    def gt(self, column, value):
+        """gt (comparison_ops.rs:7-10): !v.is_nan() && v > value per row."""
+        return self._predicate(column, L.PRED_GT, value)
+
+    def ge(self, column, value):
+        """ge (comparison_ops.rs:13-16)."""
+        return self._predicate(column, L.PRED_GE, value)
+
+    def lt(self, column, value):
+        """lt (comparison_ops.rs:19-22)."""
+        return self._predicate(column, L.PRED_LT, value)
+
+    def le(self, column, value):
+        """le (comparison_ops.rs:25-28)."""
+        return self._predicate(column, L.PRED_LE, value)
+
+    def eq_value(self, column, value):
+        """eq_value (comparison_ops.rs:31-37): !v.is_nan() && (v - value).abs() < f64::EPSILON."""
+        return self._predicate(column, L.PRED_EQ, value)
+
+    def ne_value(self, column, value):
+        """ne_value (comparison_ops.rs:40-46): v.is_nan() || (v - value).abs() >= f64::EPSILON."""
+        return self._predicate(column, L.PRED_NE, value)
+
+    def between(self, column, lower, upper):
+        """between (functions.rs:253-257): lower <= v && v <= upper."""
+        return self._predicate(column, L.PRED_BETWEEN, lower, upper)
+
+    def is_between(self, column, lower, upper, inclusive=True):
+        """is_between (functions.rs:4141-4161): between, or lower < v && v < upper when not inclusive."""
+        return self._predicate(column, L.PRED_BETWEEN if inclusive else L.PRED_BETWEEN_EXCLUSIVE, lower, upper)
+
+    def isna(self, column):
+        """isna (functions.rs:930-933): v.is_nan(); a null cell counts as NaN here."""
+        return self._predicate(column, L.PRED_ISNA)
+
+    def notna(self, column):
+        """notna (functions.rs:1312-1315)."""
+        return self._predicate(column, L.PRED_NOTNA)
+
+    def is_finite(self, column):
+        """is_finite (functions.rs:4016-4019)."""
+        return self._predicate(column, L.PRED_IS_FINITE)
+
+    def is_infinite(self, column):
+        """is_infinite (functions.rs:4021-4024)."""
+        return self._predicate(column, L.PRED_IS_INFINITE)
+
+    def count_na(self, column):
+        """count_na (functions.rs:3837-3840): the NaN (and null) cells, from the count-only form: no mask is written."""
+        return self._predicate_count(column, L.PRED_ISNA)
+
+    def has_nulls(self, column):
+        """has_nulls (functions.rs:4187-4190)."""
+        return self._predicate_count(column, L.PRED_ISNA) > 0
+
+    def count_value(self, column, value):
+        """count_value (functions.rs:4089-4095): the cells eq_value selects, counted on the device."""
+        return self._predicate_count(column, L.PRED_EQ, value)
+
+    def query_gt(self, column, value):
+        """query_gt (functions.rs:2785-2789): the rows with v > value, every column kept, assembled as filter does."""
+        return self._predicate_rows(column, L.PRED_GT, value)
+
+    def query_lt(self, column, value):
+        """query_lt (functions.rs:2791-2795)."""
+        return self._predicate_rows(column, L.PRED_LT, value)
+
+    def query_eq(self, column, value):
+        """query_eq (functions.rs:2776-2783): the rows with (v - value).abs() < f64::EPSILON."""
+        return self._predicate_rows(column, L.PRED_EQ, value)
+
+    def dropna(self, column):
+        """dropna (functions.rs:920-929): the rows whose cell is not NaN (and not null), every column kept."""
+        return self._predicate_rows(column, L.PRED_NOTNA)
+
+    def isin_numeric(self, column, values):
+        """isin_numeric (functions.rs:150-158): the cell's f64 bits are in the list's (-0.0 is not 0.0; a NaN matches the
+        same payload only).  A null cell never matches."""
+        col = self._numeric(column)
+        vals = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if col.len() == 0:
+            return []
+        bits, _ = get_context().isin(col.view(), col.len(), (vals, None, L.F64), out_device=False)
+        return np.unpackbits(bits, count=col.len(), bitorder="little").astype(bool).tolist()
+
+    def isin(self, column, values):
+        """isin (functions.rs:141-149) on a String column, through pool codes: a string the pool has never seen cannot be
+        in the column and is dropped from the list.  A null cell never matches.  Errors before any device call:
+        ColumnNotFound, ColumnTypeMismatch for a column that is not String."""
+        col = self.column(column)
+        if col.dtype != L.U32CODE:
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a string type" % column)
+        codes = [c for c in map(GLOBAL_STRING_POOL.find, values) if c is not None]
+        if col.len() == 0:
+            return []
+        bits, _ = get_context().isin(col.view(), col.len(), (np.asarray(codes, dtype=np.uint32), None, L.U32CODE), out_device=False)
+        return np.unpackbits(bits, count=col.len(), bitorder="little").astype(bool).tolist()
 
     # -- joins (join.rs:32-73) -----------------------------------------------------------------------------
     def inner_join(self, other, left_on, right_on):
