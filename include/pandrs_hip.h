@@ -215,6 +215,9 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *                       global set; 0 = the default, by the list's size (isin_lds_max_values; experiments/predicate_bench.py)
  *   "predicate_path"    tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in its loop; 0 = the
  *                       default, integers compared against the interval the host bisects (the same bits; experiments/predicate_bench.py)
+ *   "window_quantile_path"  tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, which serves rolling
+ *                       windows of at most 44 rows (a wider or expanding window: PANDRS_HIP_ERR_INVALID_ARGUMENT), 2 = it always
+ *                       takes the general (wavelet matrix) path; 0 = the default, by the window (experiments/window_quantile_bench.py)
  *   "no_runs"           1 = never the clustered-rows (RUNS) instantiation
  *   "no_direct"         1 = never the few-groups direct path (-1 = allow it below 4 M rows too)
  *   "test_throw"        tests of the exception firewall (ctx may be NULL): 1 = the entry point's host code throws std::bad_alloc
@@ -575,8 +578,8 @@ int32_t pandrs_hip_filter_gather(pandrs_hip_ctx *ctx, int32_t src_mem_space, con
  * the kind, window < 1, center not 0 / 1, ddof < 0, expanding min_periods < 0, a non-finite alpha) or n_rows >= 2^32:
  * PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written.  Workspace is sized up front (rolling min / max /
  * count: 16 bytes per row, + 8 with a null mask; EWM std / var: 1 byte per row; staging: the host column and out): a
- * memory_limit below it is PANDRS_HIP_ERR_OUT_OF_MEMORY.  Out of scope: median, quantile and apply (series/window.rs),
- * the `closed` option (accepted by the reference, never read). */
+ * memory_limit below it is PANDRS_HIP_ERR_OUT_OF_MEMORY.  Median and quantile: pandrs_hip_window_quantile below.
+ * Out of scope: apply (series/window.rs), the `closed` option (accepted by the reference, never read). */
 typedef enum pandrs_hip_window_kind {
     PANDRS_HIP_WINDOW_KIND_ROLLING = 0,
     PANDRS_HIP_WINDOW_KIND_EXPANDING = 1,
@@ -606,6 +609,52 @@ typedef struct pandrs_hip_window_spec {
 
 int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                           const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
+
+/* ---- window order statistics (rolling / expanding median and quantile) ---------------------------------------------------
+ * Rolling::{median, quantile} (src/series/window.rs:298-336) and Expanding::{median, quantile} (:494-530) over the window
+ * bounds of :163-203 / :379-400, as DataFrameRollingOps / DataFrameExpandingOps::{median, quantile} call them
+ * (dataframe/enhanced_window.rs:283-290, :464-471), and PandasCompatExt::rolling_median (pandas_compat/functions.rs:2055 over
+ * helpers/window_ops.rs:206-240).
+ *
+ * pandrs_hip_window_quantile: one order statistic of one numeric column of n_rows rows.  col is I64 (cells `as f64`) or
+ * F64, with or without a null mask.  out (in out_mem_space) receives n_rows doubles.  Window bounds, min_periods and center
+ * are pandrs_hip_window's (kind ROLLING or EXPANDING; EWM has no order statistic: PANDRS_HIP_ERR_INVALID_ARGUMENT).
+ *   Window values: the window's included cells: non-null (window.rs:192, :390), and with nan_missing = 1 also non-NaN
+ *     (window_ops.rs:221).  len = their number.  len < min_periods -> NaN (window.rs:194-199, :392-397).
+ *   Sorted order: ascending by value, -0.0 and +0.0 tied, ties in row order: the reference's stable
+ *     sort_by(partial_cmp) (window.rs:301, :326).
+ *   Median (median = 1, q ignored): mid = len / 2; odd len: sorted[mid]; even len: (sorted[mid-1] + sorted[mid]) / 2.0
+ *     (:302-307): one add and one divide, an overflow to +-inf is kept.
+ *   Quantile (median = 0): idx = min(round(q * (len-1) as f64), len-1) with Rust's round (half away from zero), the result
+ *     is sorted[idx] (:327-328).  q outside [0, 1]: PANDRS_HIP_ERR_INVALID_ARGUMENT (:318-322).
+ * Parity: bit for bit at every window size, signed zeros included: the result is a cell of the column or the exact mean
+ * of two.  Deviations:
+ *  - len == 0 (possible under min_periods 0) gives NaN; the reference underflows `mid - 1` / `len - 1` and panics;
+ *  - a NaN q is rejected; the reference's comparisons let it through and `NaN as usize` selects index 0;
+ *  - with nan_missing = 0 a window that holds a NaN value gives NaN; the reference sorts it with a comparator that is not
+ *    a total order, so its answer depends on the sort's internals.
+ * Two paths give the same bits ("window_quantile_path" forces either): rolling windows of at most 44 rows select in LDS
+ * with no workspace; every other window goes through the column's stable sort order (pandrs_hip_sort_indices' workspace
+ * and 8 bytes per row) and a wavelet matrix over the sort ranks (16 bytes per row, + 16 bytes per 64 rows for each of the
+ * bit-length-of-(n_rows-1) levels and two more).  Host columns are staged; device and resident columns are read in place
+ * (data 8-byte aligned; a null mask at any byte offset).  Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than
+ * min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a column that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a bad
+ * spec (kind, median / nan_missing / center not 0 / 1, window < 1, expanding min_periods < 0, q) or n_rows >= 2^32:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK, nothing written.  The workspace is sized up front: a memory_limit below
+ * it is PANDRS_HIP_ERR_OUT_OF_MEMORY.  pandrs_hip_get_timings: the direct path is PANDRS_HIP_PHASE_OTHER; the general path
+ * shows the sort's phases, the ranks and levels as PANDRS_HIP_PHASE_BUILD and the queries as PANDRS_HIP_PHASE_PROBE. */
+typedef struct pandrs_hip_window_quantile_spec {
+    int32_t kind;           /* PANDRS_HIP_WINDOW_KIND_ROLLING or _EXPANDING */
+    int32_t median;         /* 1: median (q ignored); 0: quantile(q) */
+    int64_t window;         /* ROLLING: window_size >= 1 */
+    int64_t min_periods;    /* ROLLING: < 0 = window; EXPANDING: >= 0 */
+    int32_t center;         /* ROLLING: 0 / 1 */
+    int32_t nan_missing;    /* 0: only null cells are missing (series/window.rs); 1: NaN cells too (window_ops.rs:221) */
+    double q;               /* quantile: 0 <= q <= 1 */
+} pandrs_hip_window_quantile_spec;
+
+int32_t pandrs_hip_window_quantile(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                                   const pandrs_hip_window_quantile_spec *spec, int32_t out_mem_space, double *out);
 
 /* ---- describe and exact percentiles of one numeric column ------------------------------------------------------------------
  * Replaces OptimizedDataFrame::describe / describe_all (src/optimized/split_dataframe/stats.rs:50-171) over stats::describe

@@ -8,6 +8,8 @@
 //                             join.rs:32-73, aggregate.rs:21-217, sort.rs:18-272, data_ops.rs:15-121,
 //                             row_ops.rs:26-130, parallel.rs:21-230, select.rs:150-167;
 //                             rolling / expanding / ewm: src/dataframe/window.rs:13-160 (series/window.rs)
+//                             rolling_median: pandas_compat/helpers/window_ops.rs:206-240; apply_rolling / apply_expanding
+//                             (median, quantile and the other operations): src/dataframe/enhanced_window.rs
 //                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
 //                             rank: src/dataframe/pandas_compat/functions.rs:193-236
 //                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
@@ -252,6 +254,27 @@ enum class AggregateOp { Sum = 0, Mean, Min, Max, Count, Std, Var, Median, First
 enum class JoinType { Inner = 0, Left, Right, Outer };                                              // join.rs:11-20
 
 class GroupBy;
+
+// ---- the window builder (dataframe/enhanced_window.rs:14-75): configurations for apply_rolling / apply_expanding ----
+struct DataFrameRolling {
+    size_t window_size;
+    int64_t min_periods_ = -1;                 // < 0: window_size (enhanced_window.rs:305)
+    bool center_ = false, has_columns_ = false;
+    std::vector<std::string> columns_;
+    explicit DataFrameRolling(size_t w) : window_size(w) {}
+    DataFrameRolling &min_periods(size_t m) { min_periods_ = (int64_t)m; return *this; }
+    DataFrameRolling &center(bool c) { center_ = c; return *this; }
+    DataFrameRolling &columns(std::vector<std::string> c) { columns_ = std::move(c); has_columns_ = true; return *this; }
+};
+struct DataFrameExpanding {
+    size_t min_periods;
+    bool has_columns_ = false;
+    std::vector<std::string> columns_;
+    explicit DataFrameExpanding(size_t m) : min_periods(m) {}
+    DataFrameExpanding &columns(std::vector<std::string> c) { columns_ = std::move(c); has_columns_ = true; return *this; }
+};
+class DataFrameRollingOps;
+class DataFrameExpandingOps;
 
 // ---- OptimizedDataFrame ------------------------------------------------------------------------------------
 class OptimizedDataFrame {
@@ -578,6 +601,63 @@ public:
         return with_window(column_name, operation, new_column_name, sp);
     }
 
+    // ---- window order statistics (helpers/window_ops.rs:206-240; dataframe/enhanced_window.rs) ----
+    // PandasCompatExt::rolling_median (pandas_compat/functions.rs:2055): the median of the trailing window's non-null,
+    // non-NaN cells; NaN where fewer than min_periods (< 0: window) of them, or none, are there; window 0 acts as 1.
+    std::vector<double> rolling_median(const std::string &column_name, size_t window, int64_t min_periods = -1) const {
+        window_column(column_name);
+        std::vector<double> out(row_count_);
+        if (row_count_) {
+            const pandrs_hip_window_quantile_spec sp{PANDRS_HIP_WINDOW_KIND_ROLLING, 1, (int64_t)std::max<size_t>(window, 1),
+                                                     min_periods < 0 ? (int64_t)window : min_periods, 0, 1, 0.5};
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_window_quantile(detail::context(), mem_space(), &v, (int64_t)row_count_, &sp, PANDRS_HIP_MEM_HOST, out.data()));
+        }
+        return out;
+    }
+    // DataFrameWindowExt::apply_rolling / apply_expanding (enhanced_window.rs:204-216): the operations of a configuration
+    inline DataFrameRollingOps apply_rolling(const DataFrameRolling &config) const;
+    inline DataFrameExpandingOps apply_expanding(const DataFrameExpanding &config) const;
+    // The builder's operations (enhanced_window.rs:317-424): every column of this frame, then a Float64Column
+    // "{column}_{operation}" per target: the given columns, else every Int64 / Float64 column.  ws: a pandrs_hip_window
+    // statistic; qs: a median / quantile.  Every error before any device call.
+    OptimizedDataFrame window_columns(const std::vector<std::string> *given, const std::string &operation, const pandrs_hip_window_spec *ws,
+                                      const pandrs_hip_window_quantile_spec *qs) const {
+        std::vector<std::string> targets;
+        if (given) {
+            for (const auto &name : *given) column(name);                                  // ColumnNotFound (:414-418)
+            targets = *given;
+        } else {
+            for (size_t c = 0; c < columns.size(); c++)
+                if (columns[c].index() <= 1) targets.push_back(column_names[c]);
+        }
+        std::vector<std::string> names = column_names;
+        for (const auto &t : targets) {
+            window_column(t);
+            if ((ws ? ws->kind : qs->kind) == PANDRS_HIP_WINDOW_KIND_ROLLING && (ws ? ws->window : qs->window) < 1)
+                throw Error(Error::InvalidValue, "Window size must be greater than 0");      // series/window.rs:112-117
+            if (qs && !qs->median && !(qs->q >= 0.0 && qs->q <= 1.0))
+                throw Error(Error::InvalidValue, "Quantile must be between 0 and 1");        // series/window.rs:318-322
+            const std::string name = t + "_" + operation;
+            if (std::find(names.begin(), names.end(), name) != names.end()) throw Error(Error::DuplicateColumnName, "Duplicate column name: " + name);
+            names.push_back(name);
+        }
+        OptimizedDataFrame result;
+        for (size_t c = 0; c < columns.size(); c++) result.add_column(column_names[c], columns[c]);
+        for (const auto &t : targets) {
+            Float64Column out;
+            out.data.resize(row_count_);
+            if (row_count_) {
+                const pandrs_hip_column v = view_of(t);
+                detail::check(ws ? pandrs_hip_window(detail::context(), mem_space(), &v, (int64_t)row_count_, ws, PANDRS_HIP_MEM_HOST, out.data.data())
+                                 : pandrs_hip_window_quantile(detail::context(), mem_space(), &v, (int64_t)row_count_, qs, PANDRS_HIP_MEM_HOST,
+                                                              out.data.data()));
+            }
+            result.add_column(t + "_" + operation, std::move(out));
+        }
+        return result;
+    }
+
 private:
     size_t row_count_ = 0;
     std::shared_ptr<detail::ResidentSet> resident_;
@@ -834,6 +914,63 @@ private:
 };
 
 // ---- GroupBy (group/types.rs:46-55) ------------------------------------------------------------------------
+// DataFrameRollingOps / DataFrameExpandingOps (enhanced_window.rs:246-425, :427-560): median and quantile go to
+// pandrs_hip_window_quantile, the others to pandrs_hip_window
+class DataFrameRollingOps {
+public:
+    DataFrameRollingOps(const OptimizedDataFrame &df, const DataFrameRolling &config) : df_(df), cfg_(config) {}
+    OptimizedDataFrame mean() const { return stat("mean", PANDRS_HIP_WINDOW_MEAN); }
+    OptimizedDataFrame sum() const { return stat("sum", PANDRS_HIP_WINDOW_SUM); }
+    OptimizedDataFrame std(size_t ddof) const { return stat("std", PANDRS_HIP_WINDOW_STD, (int64_t)ddof); }
+    OptimizedDataFrame var(size_t ddof) const { return stat("var", PANDRS_HIP_WINDOW_VAR, (int64_t)ddof); }
+    OptimizedDataFrame min() const { return stat("min", PANDRS_HIP_WINDOW_MIN); }
+    OptimizedDataFrame max() const { return stat("max", PANDRS_HIP_WINDOW_MAX); }
+    OptimizedDataFrame count() const { return stat("count", PANDRS_HIP_WINDOW_COUNT); }
+    OptimizedDataFrame median() const { return order("median", 1, 0.5); }
+    OptimizedDataFrame quantile(double q) const { return order("quantile", 0, q); }
+
+private:
+    const OptimizedDataFrame &df_;
+    const DataFrameRolling &cfg_;
+    const std::vector<std::string> *given() const { return cfg_.has_columns_ ? &cfg_.columns_ : nullptr; }
+    OptimizedDataFrame stat(const char *name, int32_t op, int64_t ddof = 1) const {
+        const pandrs_hip_window_spec sp{PANDRS_HIP_WINDOW_KIND_ROLLING, op, (int64_t)cfg_.window_size, cfg_.min_periods_ < 0 ? (int64_t)cfg_.window_size : cfg_.min_periods_, cfg_.center_ ? 1 : 0, 0, ddof, 0.0};
+        return df_.window_columns(given(), name, &sp, nullptr);
+    }
+    OptimizedDataFrame order(const char *name, int32_t median, double q) const {
+        const pandrs_hip_window_quantile_spec sp{PANDRS_HIP_WINDOW_KIND_ROLLING, median, (int64_t)cfg_.window_size, cfg_.min_periods_ < 0 ? (int64_t)cfg_.window_size : cfg_.min_periods_, cfg_.center_ ? 1 : 0, 0, q};
+        return df_.window_columns(given(), name, nullptr, &sp);
+    }
+};
+class DataFrameExpandingOps {
+public:
+    DataFrameExpandingOps(const OptimizedDataFrame &df, const DataFrameExpanding &config) : df_(df), cfg_(config) {}
+    OptimizedDataFrame mean() const { return stat("mean", PANDRS_HIP_WINDOW_MEAN); }
+    OptimizedDataFrame sum() const { return stat("sum", PANDRS_HIP_WINDOW_SUM); }
+    OptimizedDataFrame std(size_t ddof) const { return stat("std", PANDRS_HIP_WINDOW_STD, (int64_t)ddof); }
+    OptimizedDataFrame var(size_t ddof) const { return stat("var", PANDRS_HIP_WINDOW_VAR, (int64_t)ddof); }
+    OptimizedDataFrame min() const { return stat("min", PANDRS_HIP_WINDOW_MIN); }
+    OptimizedDataFrame max() const { return stat("max", PANDRS_HIP_WINDOW_MAX); }
+    OptimizedDataFrame count() const { return stat("count", PANDRS_HIP_WINDOW_COUNT); }
+    OptimizedDataFrame median() const { return order("median", 1, 0.5); }
+    OptimizedDataFrame quantile(double q) const { return order("quantile", 0, q); }
+
+private:
+    const OptimizedDataFrame &df_;
+    const DataFrameExpanding &cfg_;
+    const std::vector<std::string> *given() const { return cfg_.has_columns_ ? &cfg_.columns_ : nullptr; }
+    OptimizedDataFrame stat(const char *name, int32_t op, int64_t ddof = 1) const {
+        const pandrs_hip_window_spec sp{PANDRS_HIP_WINDOW_KIND_EXPANDING, op, 0, (int64_t)cfg_.min_periods, 0, 0, ddof, 0.0};
+        return df_.window_columns(given(), name, &sp, nullptr);
+    }
+    OptimizedDataFrame order(const char *name, int32_t median, double q) const {
+        const pandrs_hip_window_quantile_spec sp{PANDRS_HIP_WINDOW_KIND_EXPANDING, median, 0, (int64_t)cfg_.min_periods, 0, 0, q};
+        return df_.window_columns(given(), name, nullptr, &sp);
+    }
+};
+inline DataFrameRollingOps OptimizedDataFrame::apply_rolling(const DataFrameRolling &config) const { return DataFrameRollingOps(*this, config); }
+inline DataFrameExpandingOps OptimizedDataFrame::apply_expanding(const DataFrameExpanding &config) const { return DataFrameExpandingOps(*this, config); }
+
 class GroupBy {
 public:
     using Aggregation = std::tuple<std::string, AggregateOp, std::string>;      // (column, op, alias)

@@ -64,6 +64,11 @@ class WindowSpec(C.Structure):             # pandrs_hip_window_spec
                 ("center", C.c_int32), ("reserved", C.c_int32), ("ddof", C.c_int64), ("alpha", C.c_double)]
 
 
+class WindowQuantileSpec(C.Structure):     # pandrs_hip_window_quantile_spec
+    _fields_ = [("kind", C.c_int32), ("median", C.c_int32), ("window", C.c_int64), ("min_periods", C.c_int64),
+                ("center", C.c_int32), ("nan_missing", C.c_int32), ("q", C.c_double)]
+
+
 class DescribeStats(C.Structure):          # pandrs_hip_describe_stats
     _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("q1", C.c_double),
                 ("median", C.c_double), ("q3", C.c_double), ("max", C.c_double)]
@@ -151,6 +156,8 @@ SYMBOLS = {
     "pandrs_hip_filter_indices": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, _P, C.POINTER(C.c_int64)]),
     "pandrs_hip_filter_gather": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_uint64, C.c_int32, _P]),
     "pandrs_hip_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(WindowSpec), C.c_int32, _P]),
+    "pandrs_hip_window_quantile": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(WindowQuantileSpec), C.c_int32,
+                                               _P]),
     "pandrs_hip_describe": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(DescribeStats)]),
     "pandrs_hip_quantiles": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_double), C.c_int32,
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -250,6 +250,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "topk_path")) c->opt.topk_path = value;
     else if (!std::strcmp(name, "isin_path")) c->opt.isin_path = value;
     else if (!std::strcmp(name, "predicate_path")) c->opt.predicate_path = value;
+    else if (!std::strcmp(name, "window_quantile_path")) c->opt.window_quantile_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
 } catch (...) { return pandrs::on_exception("pandrs_hip_ctx_set_option"); }
@@ -484,6 +485,13 @@ int32_t pandrs_hip_window(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_h
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::window_entry(ctx, mem_space, col, n_rows, spec, out_mem_space, out);
 } catch (...) { return pandrs::on_exception("pandrs_hip_window"); }
+
+int32_t pandrs_hip_window_quantile(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                                   const pandrs_hip_window_quantile_spec *spec, int32_t out_mem_space, double *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "window_quantile: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::window_quantile_entry(ctx, mem_space, col, n_rows, spec, out_mem_space, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_window_quantile"); }
 
 int32_t pandrs_hip_describe(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                             pandrs_hip_describe_stats *out) try {

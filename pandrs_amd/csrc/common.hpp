@@ -234,6 +234,7 @@ struct Options {
     int64_t topk_path = 0;           // tests / experiments: 1 = pandrs_hip_topk always sorts the column, -1 = it always selects (0 = by the cut-over)
     int64_t isin_path = 0;           // tests / experiments: 1 = pandrs_hip_isin takes the LDS set wherever the list fits, 2 = always the global set (0 = by the list's size)
     int64_t predicate_path = 0;      // tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in the loop instead of comparing integers against the bisected interval
+    int64_t window_quantile_path = 0;   // tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, 2 = the general (wavelet matrix) path (0 = by the window)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
 
@@ -379,6 +380,9 @@ int32_t filter_gather_entry(pandrs_hip_ctx *c, int32_t src_mem_space, const pand
 size_t filter_workspace_bytes(int64_t n_rows);
 int32_t window_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                      const pandrs_hip_window_spec *spec, int32_t out_mem_space, double *out);
+// window_quantile.hip: the rolling / expanding median or quantile of one numeric column
+int32_t window_quantile_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                              const pandrs_hip_window_quantile_spec *spec, int32_t out_mem_space, double *out);
 // describe.hip: out_stats != nullptr = describe (25 / 50 / 75 and the moments), else the caller's percentiles
 int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *percentiles,
                        int32_t n_percentiles, double *out_q, int64_t *out_count, pandrs_hip_describe_stats *out_stats);

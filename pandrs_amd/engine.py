@@ -769,6 +769,32 @@ class Context:
             _raise(st)
         return out[:n] if out_device else out
 
+    def window_quantile(self, col, n_rows, kind, *, median=True, q=0.5, window=0, min_periods=-1, center=False, nan_missing=False,
+                        out_device=None):
+        """The rolling / expanding median (median=True) or quantile(q) of one I64 / F64 column on the device
+        (pandrs_hip_window_quantile; Rolling / Expanding::{median, quantile}, src/series/window.rs:298-336, :494-530, and
+        PandasCompatExt::rolling_median, helpers/window_ops.rs:206-240).  `col`, kind (L.WINDOW_KIND_ROLLING / _EXPANDING),
+        window, min_periods (< 0 = window) and center as in window(); nan_missing=True also skips NaN cells
+        (window_ops.rs:221).  A window with fewer than min_periods values, or none, gives NaN, as does (without
+        nan_missing) one that holds a NaN value.  Same return conventions as window()."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n = int(n_rows)
+        spec = L.WindowQuantileSpec(kind=int(kind), median=1 if median else 0, window=int(window), min_periods=int(min_periods),
+                                    center=1 if center else 0, nan_missing=1 if nan_missing else 0, q=float(q))
+        if out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
+        else:
+            out = np.empty(n, np.float64)
+        st = self.lib.pandrs_hip_window_quantile(self.h, sp, cc, n, C.byref(spec), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                                 _ptr(out) if n else None)
+        if st:
+            _raise(st)
+        return out[:n] if out_device else out
+
     # -- describe / exact percentiles (radix select) -------------------------------------------------------------
     def describe(self, col, n_rows):
         """count, mean, std, min, 25%, 50%, 75%, max of one I64 / F64 column on the device (pandrs_hip_describe;

@@ -565,7 +565,8 @@ class OptimizedDataFrame:
         [max(0, i+1-w), i+1), or with center start = i >= w/2 ? i - w/2 : 0, end = min(start+w, n).  operation: sum,
         mean, var, std (ddof), min, max, count, any case.  min_periods defaults to window_size.  Errors, all before any
         device call: ColumnNotFound, ColumnTypeMismatch (not Int64 / Float64), InvalidValue (window_size 0, an unknown
-        operation, median / quantile), DuplicateColumnName."""
+        operation, median / quantile), DuplicateColumnName.  The string dispatch takes no "median" / "quantile", as the
+        reference's (window.rs:54-67): they live in rolling_median and apply_rolling(config).median() / .quantile(q)."""
         col = self._window_column(column_name)
         if int(window_size) <= 0:
             raise InvalidValue("Window size must be greater than 0")            # series/window.rs:112-117
@@ -579,7 +580,8 @@ class OptimizedDataFrame:
 
     def expanding(self, min_periods, column_name, operation, new_column_name=None, *, ddof=1):
         """DataFrameWindowExt::expanding (dataframe/window.rs:82-119; Expanding, series/window.rs:379-500): row i's
-        window is [0, i+1); min_periods as given (0 allowed).  Same operations and errors as rolling."""
+        window is [0, i+1); min_periods as given (0 allowed).  Same operations and errors as rolling; the expanding
+        median and quantile live in apply_expanding(config).median() / .quantile(q)."""
         col = self._window_column(column_name)
         if int(min_periods) < 0:
             raise InvalidValue("min_periods must be >= 0")
@@ -611,6 +613,31 @@ class OptimizedDataFrame:
             raise InvalidValue("EWM alpha %r is not finite" % a)
         op = self._window_op("EWM", operation, _EWM_OPS)
         return self._with_window(col, column_name, operation, new_column_name, L.WINDOW_KIND_EWM, op, alpha=a)
+
+    # -- window order statistics (pandas_compat/helpers/window_ops.rs:206-240; dataframe/enhanced_window.rs) ------------
+    def rolling_median(self, column, window, min_periods=None):
+        """PandasCompatExt::rolling_median (pandas_compat/functions.rs:2055 over helpers/window_ops.rs:206-240): the
+        median of the trailing window's non-null, non-NaN cells, NaN where fewer than min_periods (default: window) of
+        them, or none, are there.  window 0 acts as 1 (the reference's saturating_sub).  -> a float64 numpy array.
+        Errors, before any device call: ColumnNotFound, ColumnTypeMismatch."""
+        col = self._window_column(column)
+        if int(window) < 0 or (min_periods is not None and int(min_periods) < 0):
+            raise InvalidValue("window and min_periods must be >= 0")          # (usize in the reference)
+        n = self._row_count
+        if n == 0:
+            return np.empty(0)
+        mp = int(window) if min_periods is None else int(min_periods)
+        return get_context().window_quantile(col.view(), n, L.WINDOW_KIND_ROLLING, median=True, window=max(int(window), 1),
+                                             min_periods=mp, nan_missing=True, out_device=False)
+
+    def apply_rolling(self, config):
+        """DataFrameWindowExt::apply_rolling (dataframe/enhanced_window.rs:204-209): the operations of a DataFrameRolling
+        configuration over this frame."""
+        return DataFrameRollingOps(self, config)
+
+    def apply_expanding(self, config):
+        """DataFrameWindowExt::apply_expanding (dataframe/enhanced_window.rs:211-216)."""
+        return DataFrameExpandingOps(self, config)
 
     # -- whole-column reductions (K1: split_dataframe/aggregate.rs:21-215) ----------------------------------
     def _stats(self, name):
@@ -962,6 +989,154 @@ class OptimizedDataFrame:
                 new = name + "_right" if name in result.column_indices else name
                 result.add_column(new, g.take(other.column(name), left=False))
         return result
+
+
+# ---------------------------------------------------------------- the window builder (dataframe/enhanced_window.rs)
+class DataFrameRolling:
+    """enhanced_window.rs:14-54: a rolling configuration.  window_size, then .min_periods(n), .center(bool) and
+    .columns([names]), each returning the configuration.  (`closed` is accepted by the reference and never read.)"""
+
+    def __init__(self, window_size):
+        self.window_size = int(window_size)
+        self._min_periods = None
+        self._center = False
+        self._columns = None
+
+    def min_periods(self, min_periods):
+        self._min_periods = int(min_periods)
+        return self
+
+    def center(self, center):
+        self._center = bool(center)
+        return self
+
+    def columns(self, columns):
+        self._columns = list(columns)
+        return self
+
+
+class DataFrameExpanding:
+    """enhanced_window.rs:56-75: an expanding configuration: min_periods, then .columns([names])."""
+
+    def __init__(self, min_periods):
+        self._min_periods = int(min_periods)
+        self._columns = None
+
+    def columns(self, columns):
+        self._columns = list(columns)
+        return self
+
+
+class _DataFrameWindowOps:
+    """DataFrameRollingOps / DataFrameExpandingOps (enhanced_window.rs:246-425, :427-560): every operation returns a new
+    frame: every column of this one, then a Float64Column "{column}_{operation}" per target column (:350, :404).  The
+    targets are the configured columns, else every Int64 / Float64 column (:411-424).  Every error is raised before any
+    device call: ColumnNotFound, ColumnTypeMismatch, InvalidValue, DuplicateColumnName."""
+
+    def __init__(self, frame, config):
+        self.frame = frame
+        self.config = config
+
+    def _spec(self):
+        raise NotImplementedError
+
+    def _targets(self):
+        cols = self.config._columns
+        if cols is not None:
+            for name in cols:
+                if name not in self.frame.column_indices:
+                    raise ColumnNotFound(name)
+            return list(cols)
+        return [name for name in self.frame.column_names if self.frame.column(name).dtype in (L.I64, L.F64)]
+
+    def _apply(self, operation, run, check=None):
+        frame = self.frame
+        targets = self._targets()
+        names, seen = [], set(frame.column_indices)
+        for name in targets:
+            frame._window_column(name)
+            self._validate()
+            if check is not None:
+                check()
+            out_name = "%s_%s" % (name, operation)
+            if out_name in seen:
+                raise DuplicateColumnName(out_name)
+            seen.add(out_name)
+            names.append(out_name)
+        n = frame.row_count()
+        result = OptimizedDataFrame()
+        for c in frame.column_names:
+            result.add_column(c, frame.column(c))
+        for name, out_name in zip(targets, names):
+            values = np.asarray(run(frame.column(name).view(), n), np.float64) if n else np.empty(0)
+            result.add_column(out_name, Float64Column(values))
+        return result
+
+    def _window(self, operation, op, ddof=1):
+        if int(ddof) < 0:
+            raise InvalidValue("ddof must be >= 0")
+        kind, spec = self._spec()
+        return self._apply(operation, lambda view, n: get_context().window(view, n, kind, op, ddof=int(ddof), out_device=False, **spec))
+
+    def mean(self):
+        return self._window("mean", L.WINDOW_MEAN)
+
+    def sum(self):
+        return self._window("sum", L.WINDOW_SUM)
+
+    def std(self, ddof):
+        return self._window("std", L.WINDOW_STD, ddof)
+
+    def var(self, ddof):
+        return self._window("var", L.WINDOW_VAR, ddof)
+
+    def min(self):
+        return self._window("min", L.WINDOW_MIN)
+
+    def max(self):
+        return self._window("max", L.WINDOW_MAX)
+
+    def count(self):
+        return self._window("count", L.WINDOW_COUNT)
+
+    def median(self):
+        """Rolling / Expanding::median (series/window.rs:298-315, :494-511) of every target column, on the device."""
+        kind, spec = self._spec()
+        return self._apply("median", lambda view, n: get_context().window_quantile(view, n, kind, median=True, out_device=False, **spec))
+
+    def quantile(self, q):
+        """Rolling / Expanding::quantile (series/window.rs:317-336, :513-532): sorted[min(round(q * (len-1)), len-1)].
+        q outside [0, 1] (or NaN) is InvalidValue("Quantile must be between 0 and 1")."""
+        q = float(q)
+
+        def check():
+            if not (0.0 <= q <= 1.0):
+                raise InvalidValue("Quantile must be between 0 and 1")
+        kind, spec = self._spec()
+        return self._apply("quantile", lambda view, n: get_context().window_quantile(view, n, kind, median=False, q=q, out_device=False, **spec),
+                           check)
+
+
+class DataFrameRollingOps(_DataFrameWindowOps):
+    def _validate(self):
+        if self.config.window_size <= 0:
+            raise InvalidValue("Window size must be greater than 0")            # series/window.rs:112-117
+        if self.config._min_periods is not None and self.config._min_periods < 0:
+            raise InvalidValue("min_periods must be >= 0")
+
+    def _spec(self):
+        c = self.config
+        return L.WINDOW_KIND_ROLLING, {"window": c.window_size, "min_periods": c.window_size if c._min_periods is None else c._min_periods,
+                                       "center": c._center}
+
+
+class DataFrameExpandingOps(_DataFrameWindowOps):
+    def _validate(self):
+        if self.config._min_periods < 0:
+            raise InvalidValue("min_periods must be >= 0")
+
+    def _spec(self):
+        return L.WINDOW_KIND_EXPANDING, {"min_periods": self.config._min_periods}
 
 
 def _empty_like(col):
