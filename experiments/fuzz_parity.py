@@ -9,6 +9,7 @@ import pandrs_amd as pa
 from oracle import oracle as O
 from oracle import oracle_np as ONP
 from tests.helpers import assert_groupby_equal
+from fuzz_limits import documented_limit
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -39,10 +40,11 @@ def mask(rng, n, p):
     return O.pack_mask(rng.random(n) < p) if p > 0 else None
 
 SCALE = int(os.environ.get("FUZZ_SCALE", "1"))
-fails = 0
+fails = skips = 0
 first_case = int(os.environ.get("FUZZ_FIRST", "0"))          # replay: FUZZ_FIRST=781 fuzz_parity.py 782 77001 runs case 781 alone
 for case in range(first_case, n_cases):
     rng = np.random.default_rng(seed0 * 100003 + case)
+    drawn = {}                  # what documented_limit() judges a refusal by: the inputs, never the message alone
     try:
         if rng.random() < float(os.environ.get("FUZZ_GROUPBY_FRAC", "0.7")):      # ---------------- groupby
             n = int(rng.choice([1, 7, 1000, 70_000, 300_000, 1_200_000, 5_000_000])) * (SCALE if rng.random() < 0.5 else 1)
@@ -91,6 +93,7 @@ for case in range(first_case, n_cases):
                     "no_table_order": int(rng.random() < 0.25), "p_target": int(rng.choice([0, 0, 3072, 64])),
                     "no_lean_rounds": int(rng.random() < 0.2), "no_profile_rounds": int(rng.random() < 0.25), "no_burst_kernel": int(rng.random() < 0.2), "no_window_bound": int(rng.random() < 0.1), "no_clustered": int(rng.random() < 0.15), "clustered_chunk": int(rng.choice([0, 0, 0, 4096, 1 << 20])), "clustered_max_runs_pct": int(rng.choice([0, 0, 45]))}
             for k, v in opts.items(): ctx.set_option(k, v)
+            drawn = {"kind": "groupby", "keys": keys, "n": n, "opts": opts}
             try:
                 got = ctx.groupby_agg(keys, n, vals, aggs)
                 absorbed = ctx.timings()["absorbed_rows"]
@@ -134,6 +137,7 @@ for case in range(first_case, n_cases):
             l2 = int(rng.choice([-1, -1, 0, 1]))
             tp = int(rng.choice([0, 0, 96]))                          # two-pass partition of both sides from 96 partitions up (default: 6144)
             ctx.set_option("join_no_l2", l2); ctx.set_option("two_pass_min_p", tp)
+            drawn = {"kind": "fused", "lkey": args[0], "nl": nl, "rkey": args[3], "nr": nr, "opts": {}}
             try:
                 got = ctx.join_groupby_sum(*args)
             finally:
@@ -151,6 +155,7 @@ for case in range(first_case, n_cases):
             how = int(rng.integers(0, 4))
             jg = int(rng.random() < 0.25)
             ctx.set_option("join_generic", jg)
+            drawn = {"kind": "join", "lkey": lk, "nl": nl, "rkey": rk, "nr": nr, "opts": {}}
             ctx.set_option("join_one_pass", int(rng.random() < 0.25))
             try:
                 gl, gr = ctx.join_indices(lk, nl, rk, nr, how)
@@ -173,11 +178,11 @@ for case in range(first_case, n_cases):
             desc = "join nl=%d nr=%d kd=%d space=%d how=%d generic=%d -> %d rows" % (nl, nr, kd, space, how, jg, len(gl))
         print("ok   %3d %s" % (case, desc), flush=True)
     except pa.PandrsHipError as e:
-        if "does not fit" in str(e) or "more than 64 bits" in str(e) or "2^32-row" in str(e):      # documented limits, reported loudly
-            print("skip %3d %s" % (case, str(e)[:100]), flush=True)
+        if documented_limit(str(e), drawn):      # a documented limit that the drawn inputs do reach, reported loudly
+            skips += 1; print("skip %3d %s" % (case, str(e)[:100]), flush=True)
         else:
             fails += 1; print("FAIL %3d" % case); traceback.print_exc()
     except Exception:
         fails += 1; print("FAIL %3d" % case); traceback.print_exc()
-print("fuzz done: %d cases, %d failures (%d through the clustered-rows pass)" % (n_cases, fails, n_clustered))
+print("fuzz done: %d cases, %d failures (%d through the clustered-rows pass), %d skipped at a documented limit" % (n_cases, fails, n_clustered, skips))
 sys.exit(1 if fails else 0)
