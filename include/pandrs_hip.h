@@ -937,6 +937,80 @@ int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
                         int32_t values_mem_space, const pandrs_hip_column *values, int64_t n_values, int32_t negate,
                         int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count);
 
+/* ---- running folds and lagged differences of one numeric column: cumsum, cumprod, cummax, cummin, cumcount, shift, diff ------
+ * PandasCompatExt::cumsum / cumprod / cummax / cummin (src/dataframe/pandas_compat/functions.rs:280-327), shift (:328-342),
+ * pct_change (:514-530), diff (:531-541), cumcount (:2081-2094); known answers :4411-4447, :4547-4573, :6580-6595.  One column,
+ * I64 or F64, with or without a null mask; an I64 cell is read `as f64`, as the reference's get_column_numeric_values does.  The
+ * output is F64 for every op except CUM_COUNT, which writes I64.  A NaN this library produces is the canonical quiet NaN
+ * 0x7FF8000000000000.
+ * pandrs_hip_cumulative: row i covers rows 0 .. i.
+ *   SUM    the reference's fold from +0.0: a column of only -0.0 gives +0.0, a NaN cell makes every later row NaN, +-inf behave
+ *          as IEEE.  A parallel sum rounds differently from the sequential one: with u = 2^-53, gamma_k = k u / (1 - k u) and k
+ *          the non-null rows in 0 .. i, wherever the running sum of |x| stays finite |got_i - ref_i| <= 2 gamma_k sum_{j<=i}|x_j|
+ *          (both folds are within gamma_k sum|x| of the true sum).  Integer-valued inputs whose sum|x| stays below 2^53: bit for
+ *          bit.  The state is a plain f64.
+ *   PROD   the reference's fold from 1.0.  A workgroup-local product of ordinary data leaves f64's range where no running product
+ *          does ([1e-200, 1e200, 1e200, 1e-200]), so the state is a mantissa and an integer exponent (frexp / ldexp); 0, +-inf
+ *          and NaN stay in the mantissa, where IEEE multiplication gives the reference's class and sign.  Wherever every
+ *          reference running product up to row i is normal, zero by a zero input, infinite by an infinite input, or NaN, the
+ *          relative error is at most 2 gamma_k and class and sign are exact.  The reference is sticky after a range excursion of
+ *          finite nonzero inputs (an overflow stays +-inf, an underflow to zero stays +-0, a later 0 or inf turns them into NaN):
+ *          the apply pass records the first row r whose extended-range product converts to +-inf or 0, and the rows after r are
+ *          rewritten by one more scan that starts at r + 1 from that converted value (0 and inf absorb: no second detection).
+ *   MAX / MIN  f64::max / f64::min folds from -inf / +inf, bit for bit.  A NaN cell is skipped and outputs the running value
+ *          (-inf / +inf before the first number).  Signed zeros as pandrs_hip_window's min / max: -0.0 is below +0.0.
+ *   COUNT  the rows in 0 .. i that are neither null nor NaN, exact, as I64.
+ * pandrs_hip_lag: every result bit for bit, every operation rounded on its own (no fused multiply-add).
+ *   SHIFT       out[i] = x[i - periods], any sign of periods.  A row with no source is the reference's None, and one whose
+ *               source is null is treated the same: NaN with its bit set.  |periods| >= n_rows leaves every row missing.
+ *   DIFF        rows i < periods are NaN values with bit 0 (the reference's vec![NAN; n]); every other row x[i] - x[i - periods].
+ *               periods = 0 is valid and computes x - x.
+ *   PCT_CHANGE  rows i < periods as DIFF; elsewhere prev == 0.0 (and -0.0) gives NaN, otherwise (curr - prev) / prev.
+ *   For DIFF and PCT_CHANGE a row with a null operand is NaN with its bit set; periods < 0: PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ * Deviations:
+ *  - the reference has no null mask on these paths.  Here a row under a null bit is skipped: it outputs NaN, its bit is set in
+ *    out_null_mask and the running value passes through unchanged; CUM_COUNT writes the running count there and sets no bit.
+ *  - a running product that passes through a subnormal value keeps here the bits the reference loses.
+ *  - a NaN cell that SHIFT copies arrives as the canonical NaN, whatever its payload.
+ * How (cumulative.hip): reduce then apply over contiguous spans.  The column is cut into tiles of cum_tile_rows rows and each of
+ * the grid's workgroups owns a contiguous span of whole tiles.  Kernel 1 folds every span into one summary; the prologue of
+ * kernel 2 folds the summaries of the spans before its own (at most grid states, read from L2: no third kernel, no
+ * single-workgroup pass that grows with n_rows), then scans its tiles from that carry and writes: two reads and one write of the
+ * column.  Every hand-off between workgroups is a kernel boundary; no workgroup waits for another.  A lane loads and stores two
+ * consecutive cells as 16 bytes (two 8-byte accesses when the buffer is only 8-byte aligned), a wave 128 consecutive rows per
+ * instruction, four loads in flight; the scan runs in that order: the lane's pair, a wave scan by cross-lane moves, the loads
+ * chained, the waves through LDS with one barrier per tile.  PROD launches the pair twice; the second ends at once when no row
+ * left f64's range.  Lag is one stream: a row reads x[i] and x[i - periods].
+ * Geometry (tests read it): cum_tile_rows = 2048 rows, cum_blocks_per_cu = 4, grid = min(cum_blocks_per_cu x compute units,
+ * ceil(n_rows / cum_tile_rows)) workgroups; span b holds tiles / grid tiles and one more when b < tiles % grid.
+ * Buffers: col is I64 or F64; any other dtype: PANDRS_HIP_ERR_TYPE_MISMATCH.  Host columns and outputs are staged; device and
+ * resident columns are read in place.  Data and out_data are 8-byte aligned (16 is not required); the masks may sit at any byte
+ * offset, input bits past n_rows are ignored.  out_data receives n_rows x 8 bytes.  out_null_mask receives exactly
+ * ceil(n_rows / 8) bytes, bits past n_rows in the last byte 0, and no byte beyond is touched (stored bytewise); it may be NULL.
+ * out_data or out_null_mask overlapping the column's data or mask in the same memory space: PANDRS_HIP_ERR_INVALID_ARGUMENT (the
+ * column is read twice, so the call cannot run in place).  out_n_null is a host pointer and may be NULL: the bits set.
+ * pandrs_hip_get_timings: the phase is PANDRS_HIP_PHASE_AGGREGATE, n_partitions is 0, algorithmic_bytes counts the streams run.
+ * Workspace, sized up front in one arena: one 16-byte summary per workgroup of the full grid, the excursion cell and the counter
+ * (lag: the counter only); staging: a host column and host outputs.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
+ * col / out_data, an op outside its enum, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK,
+ * nothing written, *out_n_null = 0.
+ * Out of scope: group-wise cumulative ops, clip, skipna= and reverse scans, String and Boolean columns, the legacy string frame,
+ * TimeSeries::{diff,shift,pct_change}. */
+typedef enum pandrs_hip_cum_op {
+    PANDRS_HIP_CUM_SUM = 0, PANDRS_HIP_CUM_PROD = 1, PANDRS_HIP_CUM_MAX = 2, PANDRS_HIP_CUM_MIN = 3, PANDRS_HIP_CUM_COUNT = 4
+} pandrs_hip_cum_op;
+
+typedef enum pandrs_hip_lag_op {
+    PANDRS_HIP_LAG_SHIFT = 0, PANDRS_HIP_LAG_DIFF = 1, PANDRS_HIP_LAG_PCT_CHANGE = 2
+} pandrs_hip_lag_op;
+
+int32_t pandrs_hip_cumulative(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                              int32_t op, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
+
+int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
+                       int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

@@ -396,6 +396,29 @@ public:
     // (min_by), NaN and null cells skipped; nullopt when the column holds no number.  One pandrs_hip_arg_extreme pass for both.
     std::optional<size_t> idxmax(const std::string &column_name) const { return arg_extreme(column_name, 1); }
     std::optional<size_t> idxmin(const std::string &column_name) const { return arg_extreme(column_name, 0); }
+    // cumsum / cumprod / cummax / cummin / cumcount / shift / diff / pct_change (PandasCompatExt,
+    // src/dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094): the reference's vectors from one
+    // pandrs_hip_cumulative or pandrs_hip_lag call.  Errors before any device call: ColumnNotFound, Type (a String or Boolean
+    // column); an empty column gives an empty vector.  Deviations (pandrs_hip.h): a row under a null bit is skipped and answers
+    // NaN (shift: nullopt; cumcount: the running count); a parallel cumsum is within 2 gamma_k sum|x| of the sequential one.
+    std::vector<double> cumsum(const std::string &column_name) const { return cumulative<double>(column_name, PANDRS_HIP_CUM_SUM); }
+    std::vector<double> cumprod(const std::string &column_name) const { return cumulative<double>(column_name, PANDRS_HIP_CUM_PROD); }
+    std::vector<double> cummax(const std::string &column_name) const { return cumulative<double>(column_name, PANDRS_HIP_CUM_MAX); }
+    std::vector<double> cummin(const std::string &column_name) const { return cumulative<double>(column_name, PANDRS_HIP_CUM_MIN); }
+    std::vector<size_t> cumcount(const std::string &column_name) const {
+        const std::vector<int64_t> c = cumulative<int64_t>(column_name, PANDRS_HIP_CUM_COUNT);
+        return std::vector<size_t>(c.begin(), c.end());
+    }
+    std::vector<std::optional<double>> shift(const std::string &column_name, int32_t periods) const {
+        std::vector<uint8_t> mask;
+        const std::vector<double> v = lag(column_name, PANDRS_HIP_LAG_SHIFT, periods, &mask);
+        std::vector<std::optional<double>> out(v.size());
+        for (size_t i = 0; i < v.size(); i++)
+            if (!detail::bit_at(mask, i)) out[i] = v[i];
+        return out;
+    }
+    std::vector<double> diff(const std::string &column_name, size_t periods) const { return lag(column_name, PANDRS_HIP_LAG_DIFF, (int64_t)std::min(periods, row_count_), nullptr); }
+    std::vector<double> pct_change(const std::string &column_name, size_t periods) const { return lag(column_name, PANDRS_HIP_LAG_PCT_CHANGE, (int64_t)std::min(periods, row_count_), nullptr); }
     // ffill / bfill / fillna_method / interpolate / fillna (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:789-918,
     // :3626-3683): a NEW frame from one pandrs_hip_fill call, the named column replaced (same name, same position; Float64
     // after interpolate; a null mask only when rows are still missing), the other columns copied as they are.  A cell is
@@ -689,6 +712,32 @@ private:
         if (!found) return std::nullopt;
         return (size_t)rows[which];
     }
+    // one pandrs_hip_cumulative call (op = pandrs_hip_cum_op) -> its cells (T = int64_t for COUNT, double otherwise)
+    template <typename T>
+    std::vector<T> cumulative(const std::string &column_name, int32_t op) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        std::vector<T> out(row_count_);
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_cumulative(detail::context(), mem_space(), &v, (int64_t)row_count_, op, PANDRS_HIP_MEM_HOST, out.data(), nullptr, nullptr));
+        }
+        return out;
+    }
+    // one pandrs_hip_lag call (op = pandrs_hip_lag_op) -> its cells, and the null bitmap when `mask` is given
+    std::vector<double> lag(const std::string &column_name, int32_t op, int64_t periods, std::vector<uint8_t> *mask) const {
+        const Column &c = column(column_name);
+        if (c.index() > 1) throw Error(Error::Type, "Column '" + column_name + "' is not a numeric type");
+        std::vector<double> out(row_count_);
+        if (mask) mask->assign((row_count_ + 7) / 8, 0);
+        if (row_count_) {
+            const pandrs_hip_column v = view_of(column_name);
+            detail::check(pandrs_hip_lag(detail::context(), mem_space(), &v, (int64_t)row_count_, op, periods, PANDRS_HIP_MEM_HOST, out.data(),
+                                         mask ? mask->data() : nullptr, nullptr));
+        }
+        return out;
+    }
+
     // one pandrs_hip_fill call (method = pandrs_hip_fill_method) -> the frame with the named column replaced
     OptimizedDataFrame fill(const std::string &column_name, int32_t method, uint64_t fill_bits) const {
         const Column &c = column(column_name);

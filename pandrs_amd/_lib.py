@@ -25,6 +25,8 @@ WINDOW_SUM, WINDOW_MEAN, WINDOW_VAR, WINDOW_STD, WINDOW_MIN, WINDOW_MAX, WINDOW_
 RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_FIRST, RANK_DENSE = range(5)
 FILL_FFILL, FILL_BFILL, FILL_LINEAR, FILL_VALUE = range(4)
 TOPK_LARGEST, TOPK_SMALLEST = range(2)
+CUM_SUM, CUM_PROD, CUM_MAX, CUM_MIN, CUM_COUNT = range(5)
+LAG_SHIFT, LAG_DIFF, LAG_PCT_CHANGE = range(3)
 PRED_GT, PRED_GE, PRED_LT, PRED_LE, PRED_EQ, PRED_NE, PRED_BETWEEN, PRED_BETWEEN_EXCLUSIVE, PRED_ISNA, PRED_NOTNA, PRED_IS_FINITE, \
     PRED_IS_INFINITE = range(12)
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
@@ -164,6 +166,9 @@ SYMBOLS = {
     "pandrs_hip_rank": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, _P]),
     "pandrs_hip_fill": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_uint64, C.c_int32, _P, _P,
                                     C.POINTER(C.c_int64)]),
+    "pandrs_hip_cumulative": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
+    "pandrs_hip_lag": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P,
+                                   C.POINTER(C.c_int64)]),
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

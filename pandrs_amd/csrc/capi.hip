@@ -552,6 +552,20 @@ int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
     return pandrs::isin_entry(ctx, mem_space, col, n_rows, values_mem_space, values, n_values, negate, out_mem_space, out_bits, out_count);
 } catch (...) { return pandrs::on_exception("pandrs_hip_isin"); }
 
+int32_t pandrs_hip_cumulative(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                              int32_t op, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "cumulative: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::cumulative_entry(ctx, mem_space, col, n_rows, op, out_mem_space, out_data, out_null_mask, out_n_null);
+} catch (...) { return pandrs::on_exception("pandrs_hip_cumulative"); }
+
+int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
+                       int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "lag: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::lag_entry(ctx, mem_space, col, n_rows, op, periods, out_mem_space, out_data, out_null_mask, out_n_null);
+} catch (...) { return pandrs::on_exception("pandrs_hip_lag"); }
+
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {
     if (!out_sum || !out_sum_sq || !out_count) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce_moments: bad arguments");

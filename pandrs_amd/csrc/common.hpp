@@ -404,6 +404,11 @@ int32_t predicate_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_c
 int32_t isin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t values_mem_space,
                    const pandrs_hip_column *values, int64_t n_values, int32_t negate, int32_t out_mem_space, uint8_t *out_bits,
                    int64_t *out_count);
+// cumulative.hip: running folds (op = pandrs_hip_cum_op) and lagged differences (op = pandrs_hip_lag_op) in row order
+int32_t cumulative_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, int32_t out_mem_space,
+                         void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
+int32_t lag_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, int64_t periods,
+                  int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
 int32_t reduce_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                      double out[4], int64_t *out_count, double *out_sumsq = nullptr);
 int32_t reduce_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n,

@@ -920,6 +920,73 @@ class Context:
             _raise(st)
         return out[:n], (out_mask[:nbytes] if missing.value else None), missing.value
 
+    # -- cumulative folds and lags (reduce then apply over spans; one stream) -----------------------------------------
+    def _cell_outs(self, n, sp, want_i64, out, out_mask, out_device):
+        """The (out, out_mask, out_device) a call with one 8-byte cell per row and a null bitmap writes into."""
+        nbytes = (n + 7) // 8
+        given = [b for b in (out, out_mask) if b is not None]
+        if given:
+            if len({_is_torch(b) for b in given}) != 1:
+                raise ValueError("out and out_mask must both be numpy arrays or both CUDA tensors")
+            out_device = _is_torch(given[0])
+        elif out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            want, want_mask = (torch.int64 if want_i64 else torch.float64), torch.uint8
+            good = lambda b, dt, k: b.dtype == dt and b.is_contiguous() and b.is_cuda and b.numel() >= k  # noqa: E731
+            make = lambda dt, k: torch.empty(max(k, 1), dtype=dt, device="cuda:%d" % self.device)        # noqa: E731
+        else:
+            want, want_mask = (np.int64 if want_i64 else np.float64), np.uint8
+            good = lambda b, dt, k: isinstance(b, np.ndarray) and b.dtype == dt and b.flags.c_contiguous and b.size >= k  # noqa: E731
+            make = lambda dt, k: np.empty(k, dt)                                                                       # noqa: E731
+        if out is not None and not good(out, want, n):
+            raise ValueError("out must be a contiguous %s numpy array or CUDA tensor of at least n_rows elements" % ("int64" if want_i64 else "float64"))
+        if out_mask is not None and not good(out_mask, want_mask, nbytes):
+            raise ValueError("out_mask must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
+        if given and out_device:
+            self._wait_for_producer()
+        return (make(want, n) if out is None else out), (make(want_mask, nbytes) if out_mask is None else out_mask), out_device
+
+    def cumulative(self, col, n_rows, op, out=None, out_mask=None, out_device=None):
+        """The running fold of one I64 / F64 column on the device (pandrs_hip_cumulative; PandasCompatExt::cumsum / cumprod /
+        cummax / cummin / cumcount, src/dataframe/pandas_compat/functions.rs:280-327, :2081-2094): row i covers rows 0 .. i.
+        `col` is a (data, mask, dtype) triple on the host or the device, or a ResidentColumn; op is L.CUM_SUM / PROD / MAX /
+        MIN / COUNT.  A row under a null bit is skipped: NaN with its bit set (COUNT: the running count, no bit).  `out` /
+        `out_mask`: a numpy array or torch CUDA tensor (both in the same space) of at least n_rows float64 (COUNT: int64)
+        cells / ceil(n_rows / 8) uint8 to write into.  -> (values, mask, n_null): mask is the uint8 null bitmap of the
+        result, None when n_null == 0.  Both are `out` / `out_mask` when given; else torch tensors on this context's device
+        for device / resident columns (or out_device=True), else numpy arrays."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n, op = int(n_rows), int(op)
+        out, out_mask, out_device = self._cell_outs(n, sp, op == L.CUM_COUNT, out, out_mask, out_device)
+        nulls = C.c_int64(0)
+        st = self.lib.pandrs_hip_cumulative(self.h, sp, cc, n, op, L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                            _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
+        if st:
+            _raise(st)
+        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+
+    def lag(self, col, n_rows, op, periods, out=None, out_mask=None, out_device=None):
+        """One I64 / F64 column against itself `periods` rows earlier (pandrs_hip_lag; PandasCompatExt::shift / diff /
+        pct_change, functions.rs:328-342, :514-541).  op is L.LAG_SHIFT (any sign of periods; a row without a source, or
+        with a null one, is NaN with its bit set), L.LAG_DIFF or L.LAG_PCT_CHANGE (periods >= 0; rows i < periods are NaN
+        values with bit 0; a null operand is NaN with its bit set).  Buffers and the result as Context.cumulative; values are
+        float64."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n, op, periods = int(n_rows), int(op), int(periods)
+        if not -(1 << 63) <= periods < (1 << 63):
+            raise ValueError("periods must fit int64, got %d" % periods)
+        out, out_mask, out_device = self._cell_outs(n, sp, False, out, out_mask, out_device)
+        nulls = C.c_int64(0)
+        st = self.lib.pandrs_hip_lag(self.h, sp, cc, n, op, C.c_int64(periods), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                     _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
+        if st:
+            _raise(st)
+        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+
     # -- top-k (radix select, compaction, a sort of fewer than k rows) ---------------------------------------------------
     def topk(self, col, n_rows, k, largest=True, out=None, out_device=None):
         """The first min(k, n_rows) rows of one I64 / F64 column in descending (largest) or ascending order on the device

@@ -770,6 +770,67 @@ class OptimizedDataFrame:
         (Iterator::min_by), NaN and null cells skipped; None when the column holds no number.  One device pass."""
         return self._idx_extreme(column, 0)
 
+    # -- cumulative folds and lags (dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094) ------------
+    def _cumulative(self, column_name, op):
+        """One pandrs_hip_cumulative call -> the values as a host array.  Errors before any device call: ColumnNotFound,
+        ColumnTypeMismatch for a String or Boolean column (as rank); an empty column gives an empty result."""
+        col = self._numeric(column_name)
+        if col.len() == 0:
+            return np.empty(0, np.int64 if op == L.CUM_COUNT else np.float64)
+        return np.asarray(get_context().cumulative(col.view(), col.len(), op, out_device=False)[0])
+
+    def _lag(self, column_name, op, periods):
+        col = self._numeric(column_name)
+        periods = int(periods)
+        if op != L.LAG_SHIFT and periods < 0:
+            raise InvalidValue("periods must not be negative, got %d" % periods)        # the reference takes a usize
+        if col.len() == 0:
+            return np.empty(0, np.float64), None
+        values, mask, _ = get_context().lag(col.view(), col.len(), op, periods, out_device=False)
+        return np.asarray(values), mask
+
+    def cumsum(self, column):
+        """PandasCompatExt::cumsum (functions.rs:280-291): the running sum from +0.0, -> list of float.  A NaN cell makes
+        every later row NaN.  Deviation (pandrs_hip.h): a row under a null bit is skipped and answers NaN; the parallel sum
+        is within 2 gamma_k sum|x| of the sequential one, and bit for bit on integer-valued data below 2^53."""
+        return self._cumulative(column, L.CUM_SUM).tolist()
+
+    def cumprod(self, column):
+        """PandasCompatExt::cumprod (functions.rs:292-303): the running product from 1.0, -> list of float; sticky after an
+        overflow or an underflow to zero, as the reference's fold."""
+        return self._cumulative(column, L.CUM_PROD).tolist()
+
+    def cummax(self, column):
+        """PandasCompatExt::cummax (functions.rs:304-315): the f64::max fold from -inf, NaN cells skipped, -> list of float."""
+        return self._cumulative(column, L.CUM_MAX).tolist()
+
+    def cummin(self, column):
+        """PandasCompatExt::cummin (functions.rs:316-327): the f64::min fold from +inf, NaN cells skipped, -> list of float."""
+        return self._cumulative(column, L.CUM_MIN).tolist()
+
+    def cumcount(self, column):
+        """PandasCompatExt::cumcount (functions.rs:2081-2094): the rows so far that are neither NaN nor null, -> list of int."""
+        return [int(v) for v in self._cumulative(column, L.CUM_COUNT)]
+
+    def shift(self, column, periods):
+        """PandasCompatExt::shift (functions.rs:328-342): row i takes the cell of row i - periods, -> list of float or None
+        (no source row, or a null one)."""
+        values, mask = self._lag(column, L.LAG_SHIFT, periods)
+        out = values.tolist()
+        if mask is not None:
+            for i in np.flatnonzero(np.unpackbits(mask, bitorder="little")[:len(out)]):
+                out[i] = None
+        return out
+
+    def diff(self, column, periods):
+        """PandasCompatExt::diff (functions.rs:531-541): x[i] - x[i - periods], NaN for rows i < periods, -> list of float."""
+        return self._lag(column, L.LAG_DIFF, periods)[0].tolist()
+
+    def pct_change(self, column, periods):
+        """PandasCompatExt::pct_change (functions.rs:514-530): (x[i] - prev) / prev with prev = x[i - periods]; NaN for rows
+        i < periods and where prev == 0.0, -> list of float."""
+        return self._lag(column, L.LAG_PCT_CHANGE, periods)[0].tolist()
+
     # -- missing values (dataframe/pandas_compat/functions.rs:789-918, :3626-3683) ------------------------------
     def _fill(self, column_name, method, value=None):
         """One pandrs_hip_fill call -> a NEW frame: the named column replaced (same name, same position; Float64 after
