@@ -14,6 +14,8 @@ from tests.helpers import assert_groupby_equal
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 ctx = pa.Context(0)
+if os.environ.get("FUZZ_POISON"):          # FUZZ_POISON=<byte> (0xA5, 255, 0 ...): every workspace block is filled with it before a call uses it
+    pa.Context.poison_workspace(int(os.environ["FUZZ_POISON"], 0))
 fails = taken = 0
 for case in range(int(os.environ.get("FUZZ_FIRST", "0")), n_cases):          # replay: FUZZ_FIRST=59 fuzz_absorb.py 60 31 runs case 59 alone
     rng = np.random.default_rng(seed0 * 7919 + case)

@@ -18,6 +18,8 @@ def worker(rank, world, port, n_cases, seed0):
     dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=180))
     torch.cuda.set_device(0)
     ctx = pa.Context(0)
+    if os.environ.get("FUZZ_POISON"):          # FUZZ_POISON=<byte> (0xA5, 255, 0 ...): every workspace block is filled with it before a call uses it
+        pa.Context.poison_workspace(int(os.environ["FUZZ_POISON"], 0))
 
     def all_gather(b):
         parts = [None] * world; dist.all_gather_object(parts, b); return parts

@@ -8,6 +8,7 @@ usage: fuzz_ops.py [n_cases] [seed]      case i seeds default_rng(seed * 100003 
   FUZZ_KIND=sort|filter|window|chain     restrict the draw to one kind
   FUZZ_FIRST=i                           replay: FUZZ_FIRST=17 fuzz_ops.py 18 6001 runs case 17 alone
   FUZZ_DRY=1                             no engine: the generator and the coverage summary alone
+  FUZZ_POISON=0xA5                       set_option("poison_workspace"): the library's scratch starts every call as that byte
 
 Sort cases are layout-directed: the structured part of a case (which key layout) is case mod the number of recipes, so a
 run of a few dozen cases reaches every digit width, word count and packing edge; everything else is drawn.  The pass count
@@ -34,9 +35,6 @@ DRY = os.environ.get("FUZZ_DRY", "0") == "1"
 KINDS = ("sort", "filter", "window", "chain")
 KIND = os.environ.get("FUZZ_KIND", "")
 assert KIND in ("",) + KINDS, KIND
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-first_case = int(os.environ.get("FUZZ_FIRST", "0"))
 
 SPACES = ("host", "device", "device_offset", "resident")
 DT_NAME = {L.I64: "i64", L.F64: "f64", L.U32CODE: "str", L.BOOLBITS: "bool"}
@@ -791,11 +789,16 @@ DRAW = {"sort": (draw_sort, classify_sort, run_sort, desc_sort, SORT_FEATURES),
 
 
 def main():
+    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    first_case = int(os.environ.get("FUZZ_FIRST", "0"))
     ctx = None
     if not DRY:
         import torch  # noqa: F401  (before the library's first HIP call, as bench.py does)
         import pandrs_amd as pa
         ctx = pa.Context(0)
+        if os.environ.get("FUZZ_POISON"):       # every workspace block is filled with this byte before a call uses it
+            pa.Context.poison_workspace(int(os.environ["FUZZ_POISON"], 0))
     fails = 0
     for case in range(first_case, n_cases):
         rng = np.random.default_rng(seed0 * 100003 + case)

@@ -188,6 +188,9 @@ int32_t pandrs_hip_ctx_reserve(pandrs_hip_ctx *ctx, int64_t workspace_bytes);
 /* Number of device allocations (hipMalloc) the library has made in this process: workspace arenas grow but never
  * shrink, so a repeated call of the same shape adds none — tests assert that on the steady state. */
 int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
+/* Bytes of workspace filled by the "poison_workspace" testing knob (below) since the library was loaded; stays where it
+ * is while the knob is 0. */
+int32_t pandrs_hip_workspace_poisoned_bytes(int64_t *out_bytes);
 /* Tuning / testing knobs — EVERY name the library accepts (all default to 0 = automatic unless noted; the tests and
  * experiments/ use them to force individual code paths; tests/test_abi.py checks this list against capi.hip):
  *  planning
@@ -226,6 +229,11 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations);
  *                       5 (needs a ctx) = arms the context once: the next engine run that is nested inside a call (a merge of partial
  *                       records, a run over spilled rows) throws std::bad_alloc; that call fails with OUT_OF_MEMORY and the context
  *                       serves the next call as if nothing had happened
+ *   "poison_workspace"  tests of the workspace's write-before-read discipline (process-wide; ctx may be NULL): every workspace block the
+ *                       library hands itself (each arena whenever a call sizes it, grown or reused, and the one-off tables) is filled
+ *                       with the byte (value & 0xFF) on the call's stream before the call uses it; 256 = the zero byte, 0 (default) = off:
+ *                       no fill, no launch, no synchronisation.  Resident columns and caller buffers are never touched.
+ *                       pandrs_hip_workspace_poisoned_bytes counts what was filled
  *   "no_census"         1 = the group estimate never takes its second stage (a hash-slice census of a tenth of the rows, run when the
  *                       strided sample shows singletons its repeating keys cannot explain: a long tail behind a broad hot class)
  *   "tail_groups_hint"  tests: the group estimate handed to the tail run of the absorb pass's compact spill (0 = its own sample)

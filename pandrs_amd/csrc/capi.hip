@@ -173,6 +173,12 @@ int32_t pandrs_hip_alloc_events(int64_t *out_device_allocations) try {
     return PANDRS_HIP_OK;
 } catch (...) { return pandrs::on_exception("pandrs_hip_alloc_events"); }
 
+int32_t pandrs_hip_workspace_poisoned_bytes(int64_t *out_bytes) try {
+    if (!out_bytes) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null output");
+    *out_bytes = pandrs::poisoned_bytes().load();
+    return PANDRS_HIP_OK;
+} catch (...) { return pandrs::on_exception("pandrs_hip_workspace_poisoned_bytes"); }
+
 int32_t pandrs_hip_resident_bytes(pandrs_hip_ctx *c, int64_t *out_bytes, int64_t *out_columns) try {
     if (!c) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "null ctx");
     std::lock_guard<std::mutex> lock(c->mu);
@@ -193,6 +199,12 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
             std::lock_guard<std::mutex> lock(c->mu);
             c->test_throw_nested = true;
         }
+        return PANDRS_HIP_OK;
+    }
+    if (name && !std::strcmp(name, "poison_workspace")) {
+        // tests of the workspace's write-before-read discipline (common.hpp poison_block; process-wide, needs no context)
+        if (value < 0 || value > 0x100) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "poison_workspace = %lld: 0 (off), a byte 1 ... 255, or 256 for the zero byte", (long long)value);
+        pandrs::poison_value().store(value);
         return PANDRS_HIP_OK;
     }
     if (!c || !name) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bad arguments");

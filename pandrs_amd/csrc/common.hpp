@@ -90,6 +90,29 @@ inline std::atomic<int64_t> &alloc_events() {
     return n;
 }
 
+// set_option("poison_workspace") — a testing knob, process-wide like arena_limit(): 0 = off; otherwise every workspace
+// block the library hands itself (Arena::ensure, the one-off tables) is filled with the byte (value & 0xFF) first, so a
+// kernel that reads scratch it never wrote, or that needs a zero it never stored, meets that byte instead of the
+// previous call's leftovers or a fresh allocation's zeros.  0x100 = the zero byte.
+inline std::atomic<int64_t> &poison_value() {
+    static std::atomic<int64_t> v{0};
+    return v;
+}
+// bytes filled by the hook since the library was loaded (pandrs_hip_workspace_poisoned_bytes)
+inline std::atomic<int64_t> &poisoned_bytes() {
+    static std::atomic<int64_t> n{0};
+    return n;
+}
+// off: one relaxed load, nothing else.  on: the fill runs on the call's stream and has finished on return.
+inline int32_t poison_block(void *p, size_t bytes, hipStream_t stream) {
+    const int64_t v = poison_value().load(std::memory_order_relaxed);
+    if (!v || !p || !bytes) return 0;
+    HIP_TRY(hipMemsetAsync(p, (int)(v & 0xFF), bytes, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    poisoned_bytes() += (int64_t)bytes;
+    return 0;
+}
+
 // ---- bump arena over one hipMalloc block -------------------------------------------------------
 // Sized for 288 GB of HBM: one big block per purpose, grown (never shrunk) between calls, so the
 // steady state performs no hipMalloc/hipFree inside a timed call.
@@ -99,7 +122,7 @@ struct Arena {
 
     int32_t ensure(size_t bytes, hipStream_t stream) {
         off = 0;
-        if (bytes <= cap) return 0;
+        if (bytes <= cap) return poison_block(base, cap, stream);
         if (base) {
             HIP_TRY(hipStreamSynchronize(stream));
             HIP_TRY(hipFree(base));
@@ -113,7 +136,7 @@ struct Arena {
         HIP_TRY(hipMalloc((void **)&base, want));
         alloc_events()++;
         cap = want;
-        return 0;
+        return poison_block(base, cap, stream);
     }
     template <typename T>
     T *take(size_t count) {

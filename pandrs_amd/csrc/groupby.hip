@@ -899,6 +899,7 @@ int32_t run_small(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, const 
     if (!c->small_table) {
         const size_t bytes = GS * 8 + GS * 8 * SMALL_MAX_STATES + GS * 4 + 64 * 4;
         HIP_TRY(hipMalloc(&c->small_table, bytes));
+        ST_TRY(poison_block(c->small_table, bytes, c->stream));
         HIP_TRY(hipMemsetAsync(c->small_table, 0, bytes, c->stream));
         HIP_TRY(hipMemsetAsync(c->small_table, 0xFF, GS * 8, c->stream));       // keys: EMPTY_KEY
     }

@@ -1079,6 +1079,7 @@ static int32_t census_groups(pandrs_hip_ctx *c, const KeyDesc &key, int64_t n_ro
         const size_t bytes = size_t(slots) * 8 + 256 + size_t(slots) * 4;
         HIP_TRY(hipMalloc((void **)&c->census_table, bytes));
         alloc_events()++;
+        ST_TRY(poison_block(c->census_table, bytes, c->stream));
         hipLaunchKernelGGL(estimate_clear_kernel, dim3(slots / 256), dim3(256), 0, c->stream, c->census_table, slots,
                            reinterpret_cast<uint32_t *>(c->census_table + slots), (uint32_t *)nullptr, reinterpret_cast<uint32_t *>(c->census_table + slots) + 64);
     }
@@ -1126,6 +1127,7 @@ int32_t estimate_groups(pandrs_hip_ctx *c, const KeyDesc &key, int64_t n_rows, i
         const size_t bytes = size_t(slots) * 8 + 256 + size_t(slots) * 4 + (2 * COV_BINS + 64) * 4 + EST_IMAGE_SLOTS * 8 + size_t(slots) * 4;
         HIP_TRY(hipMalloc((void **)&c->est_table, bytes));
         alloc_events()++;
+        ST_TRY(poison_block(c->est_table, bytes, c->stream));
         HIP_TRY(hipMemsetAsync(c->est_table, 0, bytes, c->stream));
         uint32_t *cnt0 = reinterpret_cast<uint32_t *>(c->est_table + slots);
         hipLaunchKernelGGL(estimate_clear_kernel, dim3(slots / 256), dim3(256), 0, c->stream, c->est_table, slots, cnt0, est_counts(c), est_sight(c));

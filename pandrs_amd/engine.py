@@ -619,6 +619,21 @@ class Context:
         L.load().pandrs_hip_alloc_events(C.byref(n))
         return n.value
 
+    @staticmethod
+    def workspace_poisoned_bytes():
+        """Bytes of workspace the "poison_workspace" knob has filled since the library was loaded."""
+        n = C.c_int64(0)
+        L.load().pandrs_hip_workspace_poisoned_bytes(C.byref(n))
+        return n.value
+
+    @staticmethod
+    def poison_workspace(byte):
+        """Testing knob (process-wide): fill every workspace block with `byte` (0 ... 255) before a call uses it; None = off."""
+        value = 0 if byte is None else (int(byte) & 0xFF) or 0x100
+        st = L.load().pandrs_hip_ctx_set_option(None, b"poison_workspace", value)
+        if st:
+            _raise(st)
+
     def comm_destroy(self):
         if getattr(self, "comm", None):
             self.lib.pandrs_hip_comm_destroy(self.comm)

@@ -77,3 +77,41 @@ def test_fuzz_ops_slice_chains():
     """filter -> gather -> sort -> gather -> window, filter -> gather -> groupby, sort -> gather -> groupby of the now clustered
     rows, sort -> gather -> window: every intermediate stays on the device, every stage is compared."""
     _run_ops("chain")
+
+
+# ---- the same sweeps with the library's workspace poisoned --------------------------------------------------------------------
+# set_option("poison_workspace") through FUZZ_POISON: every arena and one-off table starts every call as the byte instead of
+# as what the previous case left there (tests/test_gpu_workspace.py holds the directed cases, path by path; these slices add
+# the generators' variety).  Case counts: the per-case time of the slice above, measured on an MI355X, sized to about ten
+# seconds each.  The fuzz_ops slices replay the tail of the slices above (FUZZ_FIRST), so their coverage lines are not the
+# condition here.
+POISON_ENV = {"FUZZ_POISON": "0xA5"}
+FUZZ_OPS_POISONED_FIRST = {"sort": 1120 - 100, "filter": 0, "window": 920 - 590, "chain": 160 - 72}
+
+
+def test_fuzz_slice_default_mix_poisoned():
+    out = _run("fuzz_parity.py", 90, 4001, env=POISON_ENV)
+    assert "fuzz done: 90 cases, 0 failures" in out
+
+
+def test_fuzz_slice_joins_and_fused_poisoned():
+    out = _run("fuzz_parity.py", 100, 4002, env=dict(POISON_ENV, FUZZ_GROUPBY_FRAC="0.0", FUZZ_POISON="0xFF"))
+    assert "fuzz done: 100 cases, 0 failures" in out
+
+
+def test_fuzz_slice_absorb_forced_poisoned():
+    out = _run("fuzz_absorb.py", 33, 43, env=POISON_ENV)
+    assert "fuzz_absorb done: 33 cases" in out and ", 0 failures" in out
+
+
+def test_fuzz_slice_distributed_real_ranks_poisoned():
+    out = _run("fuzz_dist.py", 3, 27, 5, env=POISON_ENV)
+    assert "fuzz_dist done: world 3, 27 cases, 0 failing rank-cases" in out
+
+
+@pytest.mark.parametrize("kind", list(FUZZ_OPS_SLICES))
+def test_fuzz_ops_slice_poisoned(kind):
+    count, seed = FUZZ_OPS_SLICES[kind]
+    first = FUZZ_OPS_POISONED_FIRST[kind]
+    out = _run("fuzz_ops.py", count, seed, env=dict(POISON_ENV, FUZZ_KIND=kind, FUZZ_DRY="0", FUZZ_FIRST=str(first)))
+    assert "fuzz_ops done: %d cases, 0 failures" % (count - first) in out
