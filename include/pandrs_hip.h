@@ -1019,6 +1019,83 @@ int32_t pandrs_hip_cumulative(pandrs_hip_ctx *ctx, int32_t mem_space, const pand
 int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
                        int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
 
+/* ---- derived columns: one postfix program over up to eight columns, evaluated per row in one stream -----------------------------
+ * What the predicate and cumulative blocks above leave out (combining masks, predicates between two columns, where_cond / mask /
+ * clip) is pandrs_hip_eval.  PandasCompatExt::add_scalar / sub_scalar / mul_scalar / div_scalar / sqrt
+ * (src/dataframe/pandas_compat/functions.rs:2819-2840), col_add / col_sub / col_mul / col_div (:2851-2960), add_columns .. div_columns
+ * (:3890-3984), coalesce (:3846), clip (:237), where_cond / mask (:1079-1139), sign (:3998-4014), normalize (:2316-2337), and neg /
+ * floor / ceil / trunc / fract / reciprocal / abs_column / round_column / mod_column / floordiv (helpers/math_ops.rs) are one program
+ * each, and so is any expression over them: a * b + c > 0 costs its algorithmic bytes once, not one read and one write per operator.
+ * The program is postfix over a typed stack of values (f64) and booleans: ops[i] is a pandrs_hip_eval_op, args[i] is read by COL
+ * (a column index, integral, in [0, n_cols)) and CONST (the constant) and ignored by the rest.  Every operation is the reference's
+ * Rust expression, rounded on its own (no fused multiply-add):
+ *   COL        an I64 cell pushes (double)v (Rust's `as f64`: 2^53 + 1 loads as 2^53, as in pandrs_hip_predicate), an F64 cell its
+ *              value, a BOOLBITS cell a boolean.  A numeric cell under a null bit loads as NaN, a boolean one as false; the cell
+ *              under the bit is not read (the position of pandrs_hip_predicate and pandrs_hip_fill).  Any other dtype:
+ *              PANDRS_HIP_ERR_TYPE_MISMATCH.
+ *   CONST      pushes args[i], any f64.
+ *   ADD SUB MUL DIV   IEEE.          REM   C fmod, Rust's %.
+ *   MAX MIN    f64::max / f64::min: a NaN operand is ignored, NaN only from two NaNs; of +0.0 and -0.0 either may result.
+ *   NEG ABS FLOOR CEIL TRUNC   exact.    ROUND   half away from zero (f64::round).    FRACT   x - trunc(x).
+ *   SQRT       correctly rounded.        SIGN    1.0 / -1.0, and +0.0 for both zeros and NaN (functions.rs:3998-4014).
+ *   GT GE LT LE EQ NE   the IEEE compares of two values -> a boolean (NOT the EPSILON compare of eq_value: that is PRED_EQ).
+ *   ISNAN ISINF ISFINITE   a value -> a boolean.        AND OR NOT   booleans.
+ *   SELECT     pops b, a, cond (cond pushed first) and pushes cond ? a : b; a and b have the same type.
+ * Limits: 1 <= n_ops <= 64, 1 <= n_cols <= 8, at most 8 entries on the stack, exactly one entry left at the end, n_rows < 2^32.
+ * Output of a value program: out_data receives n_rows doubles; every NaN result is stored as 0x7FF8000000000000, so all output
+ * bits are defined.  The output null bit is set exactly where the result is NaN AND a cell of a column the program names was null
+ * in that row (whichever branch a SELECT took).  out_null_mask receives exactly ceil(n_rows / 8) bytes, bits past n_rows 0, no
+ * byte beyond touched; it may be NULL, and *out_count (a host pointer, may be NULL) is the number of such bits either way.
+ * Output of a boolean program: out_data is the bitmap with pandrs_hip_predicate's conventions: LSB-first, bit = 1 the row is
+ * selected, ceil(n_rows / 8) bytes stored bytewise, zero tail bits, any byte alignment: the data of a BOOLBITS column, which
+ * pandrs_hip_filter_indices takes in place.  out_null_mask must be NULL.  out_data may be NULL (the count only) when out_count is
+ * not; *out_count = the number of set bits.
+ * An output overlapping the data or the mask of a named column in the same memory space: PANDRS_HIP_ERR_INVALID_ARGUMENT (as
+ * pandrs_hip_lag, the call does not run in place).
+ * pandrs_hip_eval_check is the same validator with no context and no device: col_dtypes[j] is the dtype of column j;
+ * *out_is_mask = 1 for a boolean program, *out_depth = the deepest the stack gets (either may be NULL).
+ * How (eval.hip): where every entry of a postfix program sits on the stack is known before it runs, so the host lowers the program
+ * to three-address code (op, slot) and passes it by value in the kernel arguments: the dispatch is scalar and uniform, the eight
+ * slots are named registers picked by a uniform switch, nothing is indexed at run time and no kernel uses scratch.  One stream:
+ * a wave owns 128 consecutive rows per step, a lane two consecutive rows (16-byte loads and stores of 8-byte cells, two 8-byte
+ * accesses when the buffer is only 8-byte aligned); every distinct named column is loaded once per row, the result leaves with
+ * one store.  Bits leave as two wave ballots woven into the 128-row word; the count is one atomic add per workgroup.  Kernel
+ * boundaries are the only hand-off.
+ * Geometry (tests read it): eval_tile_rows = 2048 rows per workgroup iteration, eval_blocks_per_cu = 4, grid =
+ * min(eval_blocks_per_cu x compute units, ceil(n_rows / eval_tile_rows)) workgroups striding over the tiles.
+ * Buffers: the named host columns and host outputs are staged; device and resident columns are read in place; a column no COL
+ * names is not looked at.  I64 / F64 data and a value out_data are 8-byte aligned (16 is not required); BOOLBITS data, the masks
+ * and a bitmap may sit at any byte offset, input bits past n_rows are ignored.  pandrs_hip_get_timings: the phase is
+ * PANDRS_HIP_PHASE_AGGREGATE, algorithmic_bytes counts every named column and the outputs once.
+ * Workspace, sized up front: the counter; staging: the named host columns and host outputs.  A memory_limit below either is
+ * PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED (checked first); fewer rows than min_size_threshold:
+ * PANDRS_HIP_ERR_BELOW_THRESHOLD; stack underflow, an operand of the wrong type, more than one entry left, a ninth entry, an op
+ * outside 0 .. 30, a column index that is not an integer in [0, n_cols), n_ops or n_cols outside their limits, a NULL cols / ops /
+ * args, no output, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT, and pandrs_hip_last_error names the op index
+ * ("op 3: ...").  n_rows == 0: OK after the program is checked, nothing written, *out_count = 0.
+ * Out of scope: pow / log / exp (the device's libm is not glibc's), replace_numeric (a value table is pandrs_hip_isin's set),
+ * zscore, string ops and the legacy query strings, group-wise variants, the multi-GPU path. */
+typedef enum pandrs_hip_eval_op {
+    PANDRS_HIP_EVAL_COL = 0, PANDRS_HIP_EVAL_CONST = 1,
+    PANDRS_HIP_EVAL_ADD = 2, PANDRS_HIP_EVAL_SUB = 3, PANDRS_HIP_EVAL_MUL = 4, PANDRS_HIP_EVAL_DIV = 5, PANDRS_HIP_EVAL_REM = 6,
+    PANDRS_HIP_EVAL_MAX = 7, PANDRS_HIP_EVAL_MIN = 8,
+    PANDRS_HIP_EVAL_NEG = 9, PANDRS_HIP_EVAL_ABS = 10, PANDRS_HIP_EVAL_FLOOR = 11, PANDRS_HIP_EVAL_CEIL = 12, PANDRS_HIP_EVAL_TRUNC = 13,
+    PANDRS_HIP_EVAL_ROUND = 14, PANDRS_HIP_EVAL_FRACT = 15, PANDRS_HIP_EVAL_SQRT = 16, PANDRS_HIP_EVAL_SIGN = 17,
+    PANDRS_HIP_EVAL_GT = 18, PANDRS_HIP_EVAL_GE = 19, PANDRS_HIP_EVAL_LT = 20, PANDRS_HIP_EVAL_LE = 21, PANDRS_HIP_EVAL_EQ = 22,
+    PANDRS_HIP_EVAL_NE = 23,
+    PANDRS_HIP_EVAL_ISNAN = 24, PANDRS_HIP_EVAL_ISINF = 25, PANDRS_HIP_EVAL_ISFINITE = 26,
+    PANDRS_HIP_EVAL_AND = 27, PANDRS_HIP_EVAL_OR = 28, PANDRS_HIP_EVAL_NOT = 29,
+    PANDRS_HIP_EVAL_SELECT = 30             /* pops b, a, cond: cond ? a : b */
+} pandrs_hip_eval_op;
+
+int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols,
+                        int64_t n_rows, const int32_t *ops, const double *args, int32_t n_ops,
+                        int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_count);
+
+int32_t pandrs_hip_eval_check(const int32_t *col_dtypes, int32_t n_cols, const int32_t *ops, const double *args,
+                              int32_t n_ops, int32_t *out_is_mask, int32_t *out_depth);
+
 /* ---- whole-column reductions ----------------------------------------------
  * Replaces simd_{sum,mean,min,max}_{f64,i64} (src/optimized/jit/simd.rs:9-112) and
  * Int64Column/Float64Column::{sum,mean,min,max}.  out[0..3] = sum, mean, min, max as f64;

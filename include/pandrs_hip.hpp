@@ -419,6 +419,104 @@ public:
     }
     std::vector<double> diff(const std::string &column_name, size_t periods) const { return lag(column_name, PANDRS_HIP_LAG_DIFF, (int64_t)std::min(periods, row_count_), nullptr); }
     std::vector<double> pct_change(const std::string &column_name, size_t periods) const { return lag(column_name, PANDRS_HIP_LAG_PCT_CHANGE, (int64_t)std::min(periods, row_count_), nullptr); }
+    // ---- derived columns (PandasCompatExt: functions.rs:237, :1079-1139, :2316-2337, :2819-2960, :3846-4118; helpers/math_ops.rs) ----
+    // One postfix program over up to eight columns, evaluated per row in ONE pandrs_hip_eval call (pandrs_hip.h): every operation
+    // is the reference's Rust expression rounded on its own; an Int64 cell loads `as f64`, a cell under a null bit as NaN (a
+    // Boolean one as false).  eval: `names` are the columns COL 0, 1, ... stand for; a value program -> its cells (and the null
+    // bitmap when `mask` is given: a bit where the result is NaN and a named cell of the row was null); eval_mask: a boolean
+    // program -> the reference's Vec<bool>.  Errors before any device call: ColumnNotFound, Type (a String column), InvalidValue
+    // (a type or limit error of the program, from pandrs_hip_eval_check, which needs no device).
+    struct EvalOp { int32_t op; double arg; };
+    std::vector<double> eval(const std::vector<std::string> &names, const std::vector<EvalOp> &program, std::vector<uint8_t> *mask = nullptr) const {
+        if (eval_bind(names, program)) throw Error(Error::InvalidValue, "the program is a condition; eval takes a value program");
+        return eval_values(eval_views(names), mem_space(), program, mask);
+    }
+    std::vector<bool> eval_mask(const std::vector<std::string> &names, const std::vector<EvalOp> &program) const {
+        if (!eval_bind(names, program)) throw Error(Error::InvalidValue, "the program is a value; eval_mask takes a condition");
+        std::vector<uint8_t> bits((row_count_ + 7) / 8);
+        if (row_count_) {
+            const std::vector<pandrs_hip_column> v = eval_views(names);
+            std::vector<int32_t> ops;
+            std::vector<double> args;
+            for (const EvalOp &o : program) { ops.push_back(o.op); args.push_back(o.arg); }
+            detail::check(pandrs_hip_eval(detail::context(), mem_space(), v.data(), (int32_t)v.size(), (int64_t)row_count_, ops.data(), args.data(),
+                                          (int32_t)ops.size(), PANDRS_HIP_MEM_HOST, bits.data(), nullptr, nullptr));
+        }
+        return unpack(bits, row_count_);
+    }
+    // add_scalar / sub_scalar / mul_scalar / div_scalar / sqrt (functions.rs:2819-2840): the column replaced in position (Float64)
+    OptimizedDataFrame add_scalar(const std::string &c, double v) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, v}, {PANDRS_HIP_EVAL_ADD, 0}}); }
+    OptimizedDataFrame sub_scalar(const std::string &c, double v) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, v}, {PANDRS_HIP_EVAL_SUB, 0}}); }
+    OptimizedDataFrame mul_scalar(const std::string &c, double v) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, v}, {PANDRS_HIP_EVAL_MUL, 0}}); }
+    OptimizedDataFrame div_scalar(const std::string &c, double v) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, v}, {PANDRS_HIP_EVAL_DIV, 0}}); }
+    OptimizedDataFrame sqrt(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_SQRT, 0}}); }
+    // col_add .. col_div (:2851-2960), add_columns .. div_columns (:3890-3984), coalesce (:3846-3868: v1.is_nan() ? v2 : v1): the
+    // result appended as `result_name`; a name the frame already has is DuplicateColumnName (DataFrame::add_column, base.rs:143-145)
+    OptimizedDataFrame col_add(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_ADD); }
+    OptimizedDataFrame col_sub(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_SUB); }
+    OptimizedDataFrame col_mul(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_MUL); }
+    OptimizedDataFrame col_div(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_DIV); }
+    OptimizedDataFrame add_columns(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_ADD); }
+    OptimizedDataFrame sub_columns(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_SUB); }
+    OptimizedDataFrame mul_columns(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_MUL); }
+    OptimizedDataFrame div_columns(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_DIV); }
+    OptimizedDataFrame coalesce(const std::string &a, const std::string &b, const std::string &r) const { return zip_columns(a, b, r, PANDRS_HIP_EVAL_SELECT); }
+    // abs / abs_column, round / round_column ((x * f).round() / f, f = 10f64.powi(decimals) computed on the host as powi does), neg,
+    // floor, ceil, trunc, fract, reciprocal, mod_column (fmod), floordiv (helpers/math_ops.rs:29-101): the column replaced
+    OptimizedDataFrame abs(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_ABS, 0}}); }
+    OptimizedDataFrame abs_column(const std::string &c) const { return abs(c); }
+    OptimizedDataFrame round(const std::string &c, int32_t decimals) const {
+        double f = 1.0;
+        for (int32_t k = 0; k < (decimals < 0 ? -decimals : decimals); k++) f *= 10.0;         // exact up to 10^22
+        if (decimals < 0) f = 1.0 / f;
+        return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, f}, {PANDRS_HIP_EVAL_MUL, 0}, {PANDRS_HIP_EVAL_ROUND, 0}, {PANDRS_HIP_EVAL_CONST, f}, {PANDRS_HIP_EVAL_DIV, 0}});
+    }
+    OptimizedDataFrame round_column(const std::string &c, int32_t decimals) const { return round(c, decimals); }
+    OptimizedDataFrame neg(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_NEG, 0}}); }
+    OptimizedDataFrame floor(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_FLOOR, 0}}); }
+    OptimizedDataFrame ceil(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CEIL, 0}}); }
+    OptimizedDataFrame trunc(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_TRUNC, 0}}); }
+    OptimizedDataFrame fract(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_FRACT, 0}}); }
+    OptimizedDataFrame reciprocal(const std::string &c) const { return map_column(c, {{PANDRS_HIP_EVAL_CONST, 1.0}, {PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_DIV, 0}}); }
+    OptimizedDataFrame mod_column(const std::string &c, double d) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, d}, {PANDRS_HIP_EVAL_REM, 0}}); }
+    OptimizedDataFrame floordiv(const std::string &c, double d) const { return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, d}, {PANDRS_HIP_EVAL_DIV, 0}, {PANDRS_HIP_EVAL_FLOOR, 0}}); }
+    // clip (functions.rs:237-252), clip_lower (:3787), clip_upper (:3807): x.max(lower).min(upper); through f64::max / f64::min a NaN
+    // cell clips TO THE BOUND.  The column is replaced (the reference's clip fails on its own add_column of the existing name).
+    OptimizedDataFrame clip(const std::string &c, std::optional<double> lower, std::optional<double> upper) const {
+        std::vector<EvalOp> p{{PANDRS_HIP_EVAL_COL, 0}};
+        if (lower) { p.push_back({PANDRS_HIP_EVAL_CONST, *lower}); p.push_back({PANDRS_HIP_EVAL_MAX, 0}); }
+        if (upper) { p.push_back({PANDRS_HIP_EVAL_CONST, *upper}); p.push_back({PANDRS_HIP_EVAL_MIN, 0}); }
+        return map_column(c, p);
+    }
+    OptimizedDataFrame clip_lower(const std::string &c, double min) const { return clip(c, min, std::nullopt); }
+    OptimizedDataFrame clip_upper(const std::string &c, double max) const { return clip(c, std::nullopt, max); }
+    // where_cond (cond ? x : other) and mask (cond ? other : x), functions.rs:1079-1139; a condition of the wrong length: InvalidValue
+    OptimizedDataFrame where_cond(const std::string &c, const std::vector<bool> &condition, double other) const { return where_impl(c, condition, other, true); }
+    OptimizedDataFrame mask(const std::string &c, const std::vector<bool> &condition, double other) const { return where_impl(c, condition, other, false); }
+    // fillna_zero (:4097-4118: x.is_nan() ? 0.0 : x) and replace_inf (:4026-4049: x.is_infinite() ? replacement : x)
+    OptimizedDataFrame fillna_zero(const std::string &c) const {
+        return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_ISNAN, 0}, {PANDRS_HIP_EVAL_CONST, 0.0}, {PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_SELECT, 0}});
+    }
+    OptimizedDataFrame replace_inf(const std::string &c, double replacement) const {
+        return map_column(c, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_ISINF, 0}, {PANDRS_HIP_EVAL_CONST, replacement}, {PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_SELECT, 0}});
+    }
+    // sign (functions.rs:3998-4014): 1 / -1 / 0 per row, 0 for NaN and both zeros
+    std::vector<int32_t> sign(const std::string &c) const {
+        numeric(c);
+        const std::vector<double> v = eval({c}, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_SIGN, 0}});
+        return std::vector<int32_t>(v.begin(), v.end());
+    }
+    // normalize (functions.rs:2316-2337): (x - min) / (max - min), min / max over the cells that are not NaN from the whole-column
+    // reduction; InvalidValue where the reference raises it (no valid value, a range of zero)
+    std::vector<double> normalize(const std::string &c) const {
+        numeric(c);
+        if (!row_count_) throw Error(Error::InvalidValue, "No valid values in column");
+        const pandrs_hip_column_stats st = stats(c);
+        if (st.min > st.max) throw Error(Error::InvalidValue, "No valid values in column");
+        const double range = st.max - st.min;
+        if (range == 0.0) throw Error(Error::InvalidValue, "Range is zero, cannot normalize");
+        return eval({c}, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, st.min}, {PANDRS_HIP_EVAL_SUB, 0}, {PANDRS_HIP_EVAL_CONST, range}, {PANDRS_HIP_EVAL_DIV, 0}});
+    }
     // ffill / bfill / fillna_method / interpolate / fillna (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:789-918,
     // :3626-3683): a NEW frame from one pandrs_hip_fill call, the named column replaced (same name, same position; Float64
     // after interpolate; a null mask only when rows are still missing), the other columns copied as they are.  A cell is
@@ -736,6 +834,94 @@ private:
                                          mask ? mask->data() : nullptr, nullptr));
         }
         return out;
+    }
+
+    // ---- pandrs_hip_eval ----
+    void numeric(const std::string &name) const {
+        if (column(name).index() > 1) throw Error(Error::Type, "Column '" + name + "' is not a numeric type");
+    }
+    // the checks of a program that need no device -> whether it is a condition
+    bool eval_bind(const std::vector<std::string> &names, const std::vector<EvalOp> &program) const {
+        std::vector<int32_t> dtypes, ops;
+        std::vector<double> args;
+        for (const std::string &n : names) {
+            const Column &c = column(n);
+            if (c.index() == 2) throw Error(Error::Type, "Column '" + n + "' is not a numeric type");
+            dtypes.push_back(c.index() == 0 ? PANDRS_HIP_I64 : c.index() == 1 ? PANDRS_HIP_F64 : PANDRS_HIP_BOOLBITS);
+        }
+        for (const EvalOp &o : program) { ops.push_back(o.op); args.push_back(o.arg); }
+        int32_t is_mask = 0;
+        if (pandrs_hip_eval_check(dtypes.data(), (int32_t)dtypes.size(), ops.data(), args.data(), (int32_t)ops.size(), &is_mask, nullptr) != PANDRS_HIP_OK)
+            throw Error(Error::InvalidValue, pandrs_hip_last_error());
+        return is_mask != 0;
+    }
+    std::vector<pandrs_hip_column> eval_views(const std::vector<std::string> &names) const {
+        std::vector<pandrs_hip_column> v;
+        for (const std::string &n : names) v.push_back(view_of(n));
+        return v;
+    }
+    std::vector<double> eval_values(const std::vector<pandrs_hip_column> &v, int32_t space, const std::vector<EvalOp> &program, std::vector<uint8_t> *mask) const {
+        std::vector<double> out(row_count_);
+        if (mask) mask->assign((row_count_ + 7) / 8, 0);
+        if (row_count_) {
+            std::vector<int32_t> ops;
+            std::vector<double> args;
+            for (const EvalOp &o : program) { ops.push_back(o.op); args.push_back(o.arg); }
+            detail::check(pandrs_hip_eval(detail::context(), space, v.data(), (int32_t)v.size(), (int64_t)row_count_, ops.data(), args.data(),
+                                          (int32_t)ops.size(), PANDRS_HIP_MEM_HOST, out.data(), mask ? mask->data() : nullptr, nullptr));
+        }
+        return out;
+    }
+    OptimizedDataFrame with_replaced(const std::string &name, std::vector<double> values, std::vector<uint8_t> mask) const {
+        Float64Column nc;
+        nc.data = std::move(values);
+        if (std::any_of(mask.begin(), mask.end(), [](uint8_t b) { return b != 0; })) nc.null_mask = std::move(mask);
+        OptimizedDataFrame out;
+        for (size_t k = 0; k < columns.size(); k++) {
+            if (column_names[k] != name) out.add_column(column_names[k], columns[k]);
+            else out.add_column(column_names[k], nc);
+        }
+        return out;
+    }
+    OptimizedDataFrame map_column(const std::string &name, const std::vector<EvalOp> &program) const {
+        numeric(name);
+        std::vector<uint8_t> mask;
+        std::vector<double> v = eval({name}, program, &mask);
+        return with_replaced(name, std::move(v), std::move(mask));
+    }
+    // op = ADD .. DIV: a op b; SELECT: isnan(a) ? b : a
+    OptimizedDataFrame zip_columns(const std::string &a, const std::string &b, const std::string &result_name, int32_t op) const {
+        numeric(a);
+        numeric(b);
+        if (column_indices.count(result_name)) throw Error(Error::DuplicateColumnName, result_name);
+        std::vector<EvalOp> p{{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_COL, 1}, {op, 0}};
+        if (op == PANDRS_HIP_EVAL_SELECT) p = {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_ISNAN, 0}, {PANDRS_HIP_EVAL_COL, 1}, {PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_SELECT, 0}};
+        std::vector<uint8_t> mask;
+        Float64Column nc;
+        nc.data = a == b ? eval({a}, rename_second(p), &mask) : eval({a, b}, p, &mask);
+        if (std::any_of(mask.begin(), mask.end(), [](uint8_t m) { return m != 0; })) nc.null_mask = std::move(mask);
+        OptimizedDataFrame out;
+        for (size_t k = 0; k < columns.size(); k++) out.add_column(column_names[k], columns[k]);
+        out.add_column(result_name, std::move(nc));
+        return out;
+    }
+    static std::vector<EvalOp> rename_second(std::vector<EvalOp> p) {      // col_add("a", "a", ..): one distinct column
+        for (EvalOp &o : p)
+            if (o.op == PANDRS_HIP_EVAL_COL) o.arg = 0;
+        return p;
+    }
+    OptimizedDataFrame where_impl(const std::string &name, const std::vector<bool> &condition, double other, bool keep_where) const {
+        numeric(name);
+        if (condition.size() != row_count_) throw Error(Error::InvalidValue, "Condition length must match column length");       // functions.rs:1082-1086
+        std::vector<uint8_t> bits((row_count_ + 7) / 8), mask;
+        for (size_t i = 0; i < row_count_; i++)
+            if (condition[i]) bits[i >> 3] |= (uint8_t)(1u << (i & 7));
+        // the condition lives on the host, so this call reads the column's host copy too
+        const std::vector<pandrs_hip_column> v{pandrs_hip_column{bits.data(), nullptr, PANDRS_HIP_BOOLBITS, 0}, detail::view(columns[column_indices.at(name)])};
+        const std::vector<EvalOp> p = keep_where ? std::vector<EvalOp>{{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_COL, 1}, {PANDRS_HIP_EVAL_CONST, other}, {PANDRS_HIP_EVAL_SELECT, 0}}
+                                                 : std::vector<EvalOp>{{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, other}, {PANDRS_HIP_EVAL_COL, 1}, {PANDRS_HIP_EVAL_SELECT, 0}};
+        std::vector<double> out = eval_values(v, PANDRS_HIP_MEM_HOST, p, &mask);
+        return with_replaced(name, std::move(out), std::move(mask));
     }
 
     // one pandrs_hip_fill call (method = pandrs_hip_fill_method) -> the frame with the named column replaced

@@ -29,6 +29,10 @@ CUM_SUM, CUM_PROD, CUM_MAX, CUM_MIN, CUM_COUNT = range(5)
 LAG_SHIFT, LAG_DIFF, LAG_PCT_CHANGE = range(3)
 PRED_GT, PRED_GE, PRED_LT, PRED_LE, PRED_EQ, PRED_NE, PRED_BETWEEN, PRED_BETWEEN_EXCLUSIVE, PRED_ISNA, PRED_NOTNA, PRED_IS_FINITE, \
     PRED_IS_INFINITE = range(12)
+EVAL_COL, EVAL_CONST, EVAL_ADD, EVAL_SUB, EVAL_MUL, EVAL_DIV, EVAL_REM, EVAL_MAX, EVAL_MIN, EVAL_NEG, EVAL_ABS, EVAL_FLOOR, EVAL_CEIL, \
+    EVAL_TRUNC, EVAL_ROUND, EVAL_FRACT, EVAL_SQRT, EVAL_SIGN, EVAL_GT, EVAL_GE, EVAL_LT, EVAL_LE, EVAL_EQ, EVAL_NE, EVAL_ISNAN, EVAL_ISINF, \
+    EVAL_ISFINITE, EVAL_AND, EVAL_OR, EVAL_NOT, EVAL_SELECT = range(31)
+EVAL_MAX_OPS, EVAL_MAX_COLS, EVAL_MAX_DEPTH = 64, 8, 8
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -175,6 +179,10 @@ SYMBOLS = {
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "pandrs_hip_predicate": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, _P,
                                          C.POINTER(C.c_int64)]),
+    "pandrs_hip_eval": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                    C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
+    "pandrs_hip_eval_check": (C.c_int32, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pandrs_hip_isin": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32,
                                     C.c_int32, _P, C.POINTER(C.c_int64)]),
 }

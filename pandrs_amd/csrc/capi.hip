@@ -578,6 +578,19 @@ int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_
     return pandrs::lag_entry(ctx, mem_space, col, n_rows, op, periods, out_mem_space, out_data, out_null_mask, out_n_null);
 } catch (...) { return pandrs::on_exception("pandrs_hip_lag"); }
 
+int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
+                        const int32_t *ops, const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,
+                        int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "eval: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::eval_entry(ctx, mem_space, cols, n_cols, n_rows, ops, args, n_ops, out_mem_space, out_data, out_null_mask, out_count);
+} catch (...) { return pandrs::on_exception("pandrs_hip_eval"); }
+
+int32_t pandrs_hip_eval_check(const int32_t *col_dtypes, int32_t n_cols, const int32_t *ops, const double *args, int32_t n_ops,
+                              int32_t *out_is_mask, int32_t *out_depth) try {
+    return pandrs::eval_check_entry(col_dtypes, n_cols, ops, args, n_ops, out_is_mask, out_depth);
+} catch (...) { return pandrs::on_exception("pandrs_hip_eval_check"); }
+
 int32_t pandrs_hip_reduce_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n,
                                   double *out_sum, double *out_sum_sq, int64_t *out_count) try {
     if (!out_sum || !out_sum_sq || !out_count) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "reduce_moments: bad arguments");

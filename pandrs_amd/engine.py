@@ -1102,6 +1102,66 @@ class Context:
             _raise(st)
         return (None if out is None else out[:(n + 7) // 8]), cnt.value
 
+    # -- derived columns (one postfix program over up to eight columns, one stream) ---------------------------------------
+    @staticmethod
+    def eval_check(dtypes, program):
+        """The validator of pandrs_hip_eval without a context or a device (pandrs_hip_eval_check).  `dtypes`: the dtype of
+        every column; `program`: (op, arg) pairs in postfix order, op an L.EVAL_* number, arg the column index of COL and the
+        constant of CONST.  -> (is_mask, depth); raises what the call itself would."""
+        program = list(program)
+        ops, args = Context._program(program)
+        return Context._eval_check(dtypes, ops, args, len(program))
+
+    @staticmethod
+    def _eval_check(dtypes, ops, args, n_ops):
+        dts = (C.c_int32 * max(len(dtypes), 1))(*[int(d) for d in dtypes])
+        is_mask, depth = C.c_int32(0), C.c_int32(0)
+        st = L.load().pandrs_hip_eval_check(dts, len(dtypes), ops, args, n_ops, C.byref(is_mask), C.byref(depth))
+        if st:
+            _raise(st)
+        return bool(is_mask.value), depth.value
+
+    @staticmethod
+    def _program(program):
+        ops = (C.c_int32 * max(len(program), 1))(*[int(op) for op, _ in program])
+        args = (C.c_double * max(len(program), 1))(*[float(arg) for _, arg in program])
+        return ops, args
+
+    def eval(self, cols, n_rows, program, out=None, out_mask=None, out_device=None):
+        """One postfix program over up to eight columns, evaluated per row in one stream (pandrs_hip_eval): what
+        PandasCompatExt::add_scalar .. div_scalar / col_add .. col_div / clip / where_cond / round / coalesce and the like
+        (functions.rs:2819-2960, :237, :1079-1139, helpers/math_ops.rs) compute, and any expression over them, at the cost of
+        its algorithmic bytes.  `cols`: (data, mask, dtype) triples, all on the host or all on the device, or ResidentColumns
+        (I64, F64 or BOOLBITS); `program`: (op, arg) pairs as in eval_check.  Every operation is rounded on its own; a numeric
+        cell under a null bit loads as NaN, a boolean one as false.
+        A value program -> (values, mask, n_null) as Context.lag: float64 cells, every NaN canonical; a null bit where the
+        result is NaN and a named cell of the row was null.  A boolean program -> (bits, count) as Context.predicate: the
+        LSB-first bitmap filter_indices takes as (bits, None, L.BOOLBITS); `out` is then the uint8 bitmap and out_mask must be
+        None.  Results are `out` / `out_mask` when given; else torch tensors on this context's device for device / resident
+        columns (or out_device=True), else numpy arrays."""
+        cols, program = [tuple(c) for c in cols], list(program)
+        ops, args = self._program(program)
+        is_mask, _ = self._eval_check([c[2] for c in cols], ops, args, len(program))
+        keep = []
+        cc, sp = self._cols(cols, keep)
+        n = int(n_rows)
+        cnt = C.c_int64(0)
+        if is_mask:
+            if out_mask is not None:
+                raise ValueError("a boolean program takes no out_mask")
+            out, out_device = self._mask_out(n, sp, out, out_device, False)
+            st = self.lib.pandrs_hip_eval(self.h, sp, cc, len(cols), n, ops, args, len(program), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                          _ptr(out) if n else None, None, C.byref(cnt))
+            if st:
+                _raise(st)
+            return out[:(n + 7) // 8], cnt.value
+        out, out_mask, out_device = self._cell_outs(n, sp, False, out, out_mask, out_device)
+        st = self.lib.pandrs_hip_eval(self.h, sp, cc, len(cols), n, ops, args, len(program), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                      _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(cnt))
+        if st:
+            _raise(st)
+        return out[:n], (out_mask[:(n + 7) // 8] if cnt.value else None), cnt.value
+
     def isin(self, col, n_rows, values, negate=False, out=None, out_device=None, count_only=False):
         """Membership of every cell of one column in a value list on the device (pandrs_hip_isin; PandasCompatExt::isin /
         isin_numeric, functions.rs:141-158): cells are compared by their bits (-0.0 is not 0.0, a NaN matches the same payload

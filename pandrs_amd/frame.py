@@ -1007,6 +1007,299 @@ class OptimizedDataFrame:
         bits, _ = get_context().isin(col.view(), col.len(), (np.asarray(codes, dtype=np.uint32), None, L.U32CODE), out_device=False)
         return np.unpackbits(bits, count=col.len(), bitorder="little").astype(bool).tolist()
 
+    # -- derived columns (dataframe/pandas_compat/functions.rs:237, :1079-1139, :2316, :2819-2960, :3846-4110; helpers/math_ops.rs) --
+    def _bind(self, expr):
+        """An expression -> (column views, postfix program, is_mask), checked on the host before any device call:
+        ColumnNotFound, ColumnTypeMismatch for a String column (the message rank and describe use), InvalidValue for a type
+        or limit error of the program (pandrs_hip_eval_check, which needs no device)."""
+        if not isinstance(expr, Expr):
+            raise InvalidValue("expected an expression built from col() / lit() / where(), got %r" % (expr,))
+        names, program = expr.lower()
+        if not names:
+            raise InvalidValue("the expression names no column")
+        cols = [self.column(name) for name in names]
+        for name, c in zip(names, cols):
+            if c.dtype not in (L.I64, L.F64, L.BOOLBITS):
+                raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a numeric type" % name)
+        try:
+            is_mask, _ = Context.eval_check([c.dtype for c in cols], program)
+        except PandrsHipError as e:
+            raise InvalidValue(str(e))
+        return [c.view() for c in cols], program, is_mask
+
+    def _eval_values(self, expr):
+        """One pandrs_hip_eval call of a value expression -> a Float64Column (a null mask only where rows are null)."""
+        views, program, is_mask = self._bind(expr)
+        if is_mask:
+            raise InvalidValue("the expression is a condition; a column takes a value (use where(cond, a, b))")
+        if self._row_count == 0:
+            return Float64Column([])
+        values, mask, _ = get_context().eval(views, self._row_count, program, out_device=False)
+        new = Float64Column(values)
+        new.null_mask = mask
+        return new
+
+    def _replaced(self, column_name, new):
+        """A NEW frame with the named column replaced in position, the others shared, as _fill builds its result."""
+        result = OptimizedDataFrame()
+        for name in self.column_names:
+            result.add_column(name, new if name == column_name else self.column(name))
+        return result
+
+    def _map_column(self, column_name, make):
+        """`make(col(column_name))` evaluated in one call -> the frame with that column replaced.  Errors before any device
+        call: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column (as rank and describe)."""
+        self._numeric(column_name)
+        return self._replaced(column_name, self._eval_values(make(col(column_name))))
+
+    def _zip_columns(self, col1, col2, result_name, make):
+        """`make(col(col1), col(col2))` in one call -> the frame with the result appended as `result_name`; a name the
+        frame already has is DuplicateColumnName, as the reference's DataFrame::add_column (dataframe/base.rs:143-145)."""
+        self._numeric(col1), self._numeric(col2)
+        if result_name in self.column_indices:
+            raise DuplicateColumnName(result_name)
+        new = self._eval_values(make(col(col1), col(col2)))
+        result = OptimizedDataFrame()
+        for name in self.column_names:
+            result.add_column(name, self.column(name))
+        return result.add_column(result_name, new)
+
+    def with_column(self, name, expr):
+        """A NEW frame with the value expression `expr` (col("a") * col("b") + 1.0, where(cond, a, b), ...) evaluated in ONE
+        pandrs_hip_eval call as the Float64 column `name`: replaced in position when the frame has it, appended otherwise."""
+        new = self._eval_values(expr)
+        if name in self.column_indices:
+            return self._replaced(name, new)
+        result = OptimizedDataFrame()
+        for n in self.column_names:
+            result.add_column(n, self.column(n))
+        return result.add_column(name, new)
+
+    def mask_of(self, expr):
+        """The condition `expr` (col("a") > col("b"), (x > 0) & ~y.isnan(), ...) per row, from one pandrs_hip_eval call ->
+        list of bool."""
+        views, program, is_mask = self._bind(expr)
+        if not is_mask:
+            raise InvalidValue("the expression is a value; a mask takes a condition")
+        if self._row_count == 0:
+            return []
+        bits, _ = get_context().eval(views, self._row_count, program, out_device=False)
+        return np.unpackbits(bits, count=self._row_count, bitorder="little").astype(bool).tolist()
+
+    def filter_expr(self, expr):
+        """The rows where the condition `expr` holds, every column kept, assembled as filter does: pandrs_hip_eval ->
+        filter_indices on the device mask -> filter_gather per column; the mask does not visit the host."""
+        views, program, is_mask = self._bind(expr)
+        if not is_mask:
+            raise InvalidValue("the expression is a value; a filter takes a condition")
+        if self._row_count == 0:
+            return self._empty_columns()
+        bits, _ = get_context().eval(views, self._row_count, program, out_device=True)
+        return self._compact((bits, None, L.BOOLBITS))[0]
+
+    def add_scalar(self, column, value):
+        """add_scalar (functions.rs:2819-2821): x + value, the column replaced (Float64)."""
+        return self._map_column(column, lambda x: x + float(value))
+
+    def sub_scalar(self, column, value):
+        """sub_scalar (functions.rs:2827-2829): x - value."""
+        return self._map_column(column, lambda x: x - float(value))
+
+    def mul_scalar(self, column, value):
+        """mul_scalar (functions.rs:2823-2825): x * value."""
+        return self._map_column(column, lambda x: x * float(value))
+
+    def div_scalar(self, column, value):
+        """div_scalar (functions.rs:2831-2833): x / value."""
+        return self._map_column(column, lambda x: x / float(value))
+
+    def sqrt(self, column):
+        """sqrt (functions.rs:2839-2841): x.sqrt(), correctly rounded; NaN for a negative cell."""
+        return self._map_column(column, lambda x: x.sqrt())
+
+    def col_add(self, col1, col2, result_name):
+        """col_add (functions.rs:2851-2877): a + b appended as `result_name`."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a + b)
+
+    def col_sub(self, col1, col2, result_name):
+        """col_sub (functions.rs:2907-2933): a - b."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a - b)
+
+    def col_mul(self, col1, col2, result_name):
+        """col_mul (functions.rs:2879-2905): a * b."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a * b)
+
+    def col_div(self, col1, col2, result_name):
+        """col_div (functions.rs:2935-2960): a / b."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a / b)
+
+    def add_columns(self, col1, col2, result_name):
+        """add_columns (functions.rs:3890-3912): v1 + v2 appended as `result_name`."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a + b)
+
+    def sub_columns(self, col1, col2, result_name):
+        """sub_columns (functions.rs:3914-3936): v1 - v2."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a - b)
+
+    def mul_columns(self, col1, col2, result_name):
+        """mul_columns (functions.rs:3938-3960): v1 * v2."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a * b)
+
+    def div_columns(self, col1, col2, result_name):
+        """div_columns (functions.rs:3962-3984): v1 / v2."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: a / b)
+
+    def coalesce(self, col1, col2, result_name):
+        """coalesce (functions.rs:3846-3868): v1.is_nan() ? v2 : v1 appended as `result_name`; a null cell counts as NaN."""
+        return self._zip_columns(col1, col2, result_name, lambda a, b: where(a.isnan(), b, a))
+
+    def abs(self, column):
+        """abs (functions.rs:691-709): x.abs(), the column replaced."""
+        return self._map_column(column, lambda x: x.abs())
+
+    def abs_column(self, column):
+        """abs_column (functions.rs:3713-3715, helpers/math_ops.rs:64-69)."""
+        return self.abs(column)
+
+    def round(self, column, decimals):
+        """round (functions.rs:711-730): (x * f).round() / f with f = 10f64.powi(decimals), half away from zero; f is
+        computed on the host the way powi does (the exact power, its reciprocal for negative decimals)."""
+        decimals = int(decimals)
+        f = 10.0 ** abs(decimals)
+        if decimals < 0:
+            f = 1.0 / f
+        return self._map_column(column, lambda x: (x * f).round() / f)
+
+    def round_column(self, column, decimals):
+        """round_column (functions.rs:3717-3719, helpers/math_ops.rs:71-80)."""
+        return self.round(column, decimals)
+
+    def neg(self, column):
+        """neg (functions.rs:3994-3996, helpers/math_ops.rs:82-87): -x."""
+        return self._map_column(column, lambda x: -x)
+
+    def floor(self, column):
+        """floor (functions.rs:4069-4071, helpers/math_ops.rs:29-34)."""
+        return self._map_column(column, lambda x: x.floor())
+
+    def ceil(self, column):
+        """ceil (functions.rs:4073-4075, helpers/math_ops.rs:36-41)."""
+        return self._map_column(column, lambda x: x.ceil())
+
+    def trunc(self, column):
+        """trunc (functions.rs:4077-4079, helpers/math_ops.rs:43-48)."""
+        return self._map_column(column, lambda x: x.trunc())
+
+    def fract(self, column):
+        """fract (functions.rs:4081-4083, helpers/math_ops.rs:50-55): x - x.trunc()."""
+        return self._map_column(column, lambda x: x.fract())
+
+    def reciprocal(self, column):
+        """reciprocal (functions.rs:4085-4087, helpers/math_ops.rs:57-62): 1.0 / x."""
+        return self._map_column(column, lambda x: 1.0 / x)
+
+    def mod_column(self, column, divisor):
+        """mod_column (functions.rs:3986-3988, helpers/math_ops.rs:89-94): x % divisor, C's fmod."""
+        return self._map_column(column, lambda x: x % float(divisor))
+
+    def floordiv(self, column, divisor):
+        """floordiv (functions.rs:3990-3992, helpers/math_ops.rs:96-101): (x / divisor).floor()."""
+        return self._map_column(column, lambda x: (x / float(divisor)).floor())
+
+    def clip(self, column, lower=None, upper=None):
+        """clip (functions.rs:237-252): x.max(lower) then .min(upper), either bound optional.  Through f64::max / f64::min a
+        NaN cell clips TO THE BOUND.  The column is replaced (the reference's own add_column of the existing name fails with
+        DuplicateColumnName; clip_lower / clip_upper show what is meant)."""
+        def make(x):
+            if lower is not None:
+                x = x.max(float(lower))
+            if upper is not None:
+                x = x.min(float(upper))
+            return x if lower is not None or upper is not None else x + lit(-0.0)      # (the identity, still one program)
+        return self._map_column(column, make)
+
+    def clip_lower(self, column, min):
+        """clip_lower (functions.rs:3787-3805): x.max(min)."""
+        return self._map_column(column, lambda x: x.max(float(min)))
+
+    def clip_upper(self, column, max):
+        """clip_upper (functions.rs:3807-3825): x.min(max)."""
+        return self._map_column(column, lambda x: x.min(float(max)))
+
+    def _cond_expr(self, condition):
+        """The condition of where_cond / mask as an expression over one more BOOLBITS column: a list of bool, a BooleanColumn
+        or a device mask (the bits of predicate(..., out_device=True)).  A wrong length raises InvalidValue
+        (functions.rs:1082-1086)."""
+        if isinstance(condition, BooleanColumn):
+            length, view = condition.len(), condition.view()
+        elif type(condition).__module__.startswith("torch"):
+            length, view = self._row_count if condition.numel() == (self._row_count + 7) // 8 else -1, (condition, None, L.BOOLBITS)
+        else:
+            cond = np.asarray(condition, dtype=bool).reshape(-1)
+            length, view = cond.shape[0], (np.packbits(cond, bitorder="little"), None, L.BOOLBITS)
+        if length != self._row_count:
+            raise InvalidValue("Condition length must match column length")
+        return view
+
+    def _where(self, column, condition, other, keep_where):
+        c = self._numeric(column)
+        cond = self._cond_expr(condition)
+        if self._row_count == 0:
+            return self._replaced(column, Float64Column([]))
+        program = [(L.EVAL_COL, 0), (L.EVAL_COL, 1), (L.EVAL_CONST, float(other)), (L.EVAL_SELECT, 0)] if keep_where else \
+                  [(L.EVAL_COL, 0), (L.EVAL_CONST, float(other)), (L.EVAL_COL, 1), (L.EVAL_SELECT, 0)]
+        ctx = get_context()
+        view, resident = c.view(), None
+        if type(cond[0]).__module__.startswith("torch"):                 # the mask lives on the device: so does the column for this call
+            view = resident = ctx.upload_column_n(c.data, c.null_mask, c.dtype, self._row_count)
+        try:
+            values, mask, _ = ctx.eval([cond, view], self._row_count, program, out_device=False)
+        finally:
+            if resident is not None:
+                resident.release()
+        new = Float64Column(np.asarray(values))
+        new.null_mask = None if mask is None else np.asarray(mask)
+        return self._replaced(column, new)
+
+    def where_cond(self, column, condition, other):
+        """where_cond (functions.rs:1079-1108): cond ? x : other per row, the column replaced.  `condition`: a list of bool,
+        a BooleanColumn (a null condition is false) or a device mask from Context.predicate(..., out_device=True), which
+        does not visit the host."""
+        return self._where(column, condition, other, True)
+
+    def mask(self, column, condition, other):
+        """mask (functions.rs:1110-1139): cond ? other : x per row."""
+        return self._where(column, condition, other, False)
+
+    def fillna_zero(self, column):
+        """fillna_zero (functions.rs:4097-4118): x.is_nan() ? 0.0 : x; a null cell counts as NaN."""
+        return self._map_column(column, lambda x: where(x.isnan(), lit(0.0), x))
+
+    def replace_inf(self, column, replacement):
+        """replace_inf (functions.rs:4026-4049): x.is_infinite() ? replacement : x."""
+        return self._map_column(column, lambda x: where(x.isinf(), lit(float(replacement)), x))
+
+    def sign(self, column):
+        """sign (functions.rs:3998-4014): 1 / -1 / 0 per row (0 for NaN and both zeros), -> list of int."""
+        self._numeric(column)
+        return [int(v) for v in self._eval_values(col(column).sign()).data]
+
+    def normalize(self, column):
+        """normalize (functions.rs:2316-2337): (x - min) / (max - min) with min / max over the cells that are not NaN
+        (value_range, :2270-2282; the whole-column reduction, exact in any order), NaN stays NaN, -> list of float.
+        InvalidValue where the reference raises it: no valid value, or a range of zero."""
+        c = self._numeric(column)
+        if c.len() == 0:
+            raise InvalidValue("No valid values in column")
+        st = get_context().column_stats(c.view(), c.len())
+        lo, hi = float(st["min"]), float(st["max"])
+        if lo > hi:                                                      # the fold identities: no cell that is not NaN
+            raise InvalidValue("No valid values in column")
+        rng = hi - lo
+        if rng == 0.0:
+            raise InvalidValue("Range is zero, cannot normalize")
+        return self._eval_values((col(column) - lo) / rng).data.tolist()
+
     # -- joins (join.rs:32-73) -----------------------------------------------------------------------------
     def inner_join(self, other, left_on, right_on):
         return self._join_impl(other, left_on, right_on, JoinType.Inner)
@@ -1050,6 +1343,121 @@ class OptimizedDataFrame:
                 new = name + "_right" if name in result.column_indices else name
                 result.add_column(new, g.take(other.column(name), left=False))
         return result
+
+
+# ---------------------------------------------------------------- expressions over columns (pandrs_hip_eval)
+_EXPR_ARITY = {L.EVAL_ADD: 2, L.EVAL_SUB: 2, L.EVAL_MUL: 2, L.EVAL_DIV: 2, L.EVAL_REM: 2, L.EVAL_MAX: 2, L.EVAL_MIN: 2,
+               L.EVAL_GT: 2, L.EVAL_GE: 2, L.EVAL_LT: 2, L.EVAL_LE: 2, L.EVAL_EQ: 2, L.EVAL_NE: 2, L.EVAL_AND: 2, L.EVAL_OR: 2,
+               L.EVAL_SELECT: 3}
+
+
+class Expr:
+    """A row-wise expression over the columns of a frame, built with col(), lit(), where() and the operators below, and
+    evaluated by OptimizedDataFrame.with_column / mask_of / filter_expr in ONE device call (pandrs_hip_eval): every
+    operation is the reference's Rust expression rounded on its own.  + - * / % (fmod) and unary - act on values; > >= <
+    <= == != compare two values the IEEE way (not eq_value's EPSILON compare) and give a condition; & | ~ combine
+    conditions.  A plain number stands for lit(number)."""
+    __hash__ = None
+
+    def __init__(self, op, arg=0.0, children=()):
+        self.op, self.arg, self.children = op, arg, tuple(children)
+
+    @staticmethod
+    def _of(x):
+        if isinstance(x, Expr):
+            return x
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise InvalidValue("an expression takes expressions and numbers, got %r" % (x,))
+        return Expr(L.EVAL_CONST, float(x))
+
+    def _bin(self, op, other, swap=False):
+        a, b = self, Expr._of(other)
+        return Expr(op, children=(b, a) if swap else (a, b))
+
+    def lower(self):
+        """-> (the distinct column names in first-use order, the postfix program as (op, arg) pairs)."""
+        names, program = [], []
+
+        def walk(e):
+            for c in e.children:
+                walk(c)
+            if e.op == L.EVAL_COL:
+                if e.arg not in names:
+                    names.append(e.arg)
+                program.append((L.EVAL_COL, float(names.index(e.arg))))
+            else:
+                program.append((e.op, float(e.arg)))
+        walk(self)
+        return names, program
+
+    def __add__(self, o): return self._bin(L.EVAL_ADD, o)
+    def __radd__(self, o): return self._bin(L.EVAL_ADD, o, True)
+    def __sub__(self, o): return self._bin(L.EVAL_SUB, o)
+    def __rsub__(self, o): return self._bin(L.EVAL_SUB, o, True)
+    def __mul__(self, o): return self._bin(L.EVAL_MUL, o)
+    def __rmul__(self, o): return self._bin(L.EVAL_MUL, o, True)
+    def __truediv__(self, o): return self._bin(L.EVAL_DIV, o)
+    def __rtruediv__(self, o): return self._bin(L.EVAL_DIV, o, True)
+    def __mod__(self, o): return self._bin(L.EVAL_REM, o)
+    def __rmod__(self, o): return self._bin(L.EVAL_REM, o, True)
+    def __neg__(self): return Expr(L.EVAL_NEG, children=(self,))
+    def __abs__(self): return self.abs()
+    def __gt__(self, o): return self._bin(L.EVAL_GT, o)
+    def __ge__(self, o): return self._bin(L.EVAL_GE, o)
+    def __lt__(self, o): return self._bin(L.EVAL_LT, o)
+    def __le__(self, o): return self._bin(L.EVAL_LE, o)
+    def __eq__(self, o): return self._bin(L.EVAL_EQ, o)
+    def __ne__(self, o): return self._bin(L.EVAL_NE, o)
+    def __and__(self, o): return self._bin(L.EVAL_AND, o)
+    def __rand__(self, o): return self._bin(L.EVAL_AND, o, True)
+    def __or__(self, o): return self._bin(L.EVAL_OR, o)
+    def __ror__(self, o): return self._bin(L.EVAL_OR, o, True)
+    def __invert__(self): return Expr(L.EVAL_NOT, children=(self,))
+
+    def __bool__(self):
+        raise InvalidValue("an expression has no truth value; combine conditions with & | ~")
+
+    def abs(self): return Expr(L.EVAL_ABS, children=(self,))
+    def floor(self): return Expr(L.EVAL_FLOOR, children=(self,))
+    def ceil(self): return Expr(L.EVAL_CEIL, children=(self,))
+    def trunc(self): return Expr(L.EVAL_TRUNC, children=(self,))
+    def fract(self): return Expr(L.EVAL_FRACT, children=(self,))
+    def sqrt(self): return Expr(L.EVAL_SQRT, children=(self,))
+    def sign(self): return Expr(L.EVAL_SIGN, children=(self,))
+    def isnan(self): return Expr(L.EVAL_ISNAN, children=(self,))
+    def isinf(self): return Expr(L.EVAL_ISINF, children=(self,))
+    def isfinite(self): return Expr(L.EVAL_ISFINITE, children=(self,))
+
+    def round(self):
+        """f64::round: half away from zero."""
+        return Expr(L.EVAL_ROUND, children=(self,))
+
+    def max(self, o):
+        """f64::max: a NaN operand is ignored."""
+        return self._bin(L.EVAL_MAX, o)
+
+    def min(self, o):
+        """f64::min: a NaN operand is ignored."""
+        return self._bin(L.EVAL_MIN, o)
+
+    def clip(self, lower, upper):
+        """x.max(lower).min(upper), the reference's clip (functions.rs:237-245): a NaN clips to the bound."""
+        return self.max(lower).min(upper)
+
+
+def col(name):
+    """The column `name` of the frame the expression is evaluated on."""
+    return Expr(L.EVAL_COL, name)
+
+
+def lit(value):
+    """The constant `value` as f64."""
+    return Expr._of(float(value))
+
+
+def where(cond, a, b):
+    """cond ? a : b per row; a and b are both values or both conditions."""
+    return Expr(L.EVAL_SELECT, children=(Expr._of(cond), Expr._of(a), Expr._of(b)))
 
 
 # ---------------------------------------------------------------- the window builder (dataframe/enhanced_window.rs)
