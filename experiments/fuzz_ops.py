@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Randomised parity sweep for pandrs_hip_sort_indices, pandrs_hip_filter_indices / pandrs_hip_filter_gather,
 pandrs_hip_window and chains of them with every intermediate left on the device, against the restatements the GPU tests
-trust (tests/sort_ref.py, tests/window_ref.py, tests/helpers.filter_ref) and the CPU oracle.  GPU box only, except
-FUZZ_DRY=1: draw and classify every case, no engine call (the coverage condition, checked by tests/test_references.py).
+trust (tests/sort_ref.py, tests/window_ref.py, tests/helpers.filter_ref) and the CPU oracle; and, in fuzz_columns.py and
+fuzz_chain2.py, for the column ops (describe / quantiles, rank, fill, topk / arg_extreme, predicate / isin, window_quantile,
+cumulative / lag, eval) and the chains across them, against the twins under tests/*_ref.py.  GPU box only, except FUZZ_DRY:
+1 draws and classifies every case with no engine call (the coverage condition, checked by tests/test_references.py), 2 also
+computes every reference result of the newer kinds (a generator its twin cannot follow fails without a GPU; row counts capped).
 
 usage: fuzz_ops.py [n_cases] [seed]      case i seeds default_rng(seed * 100003 + i)
-  FUZZ_KIND=sort|filter|window|chain     restrict the draw to one kind
+  FUZZ_KIND=sort|filter|window|chain     restrict the draw to one kind; also describe|rank|fill|topk|predicate|wquant|cum|eval|chain2
   FUZZ_FIRST=i                           replay: FUZZ_FIRST=17 fuzz_ops.py 18 6001 runs case 17 alone
-  FUZZ_DRY=1                             no engine: the generator and the coverage summary alone
+  FUZZ_DRY=1                             no engine: the generator and the coverage summary alone (2: and the references)
   FUZZ_POISON=0xA5                       set_option("poison_workspace"): the library's scratch starts every call as that byte
 
 Sort cases are layout-directed: the structured part of a case (which key layout) is case mod the number of recipes, so a
@@ -17,89 +20,24 @@ the header documents.  A whole 64-bit word of the packed key cannot be constant 
 has 64 constant bits below it), so the nearest reachable layouts are drawn instead: 62 constant bits in a word's middle,
 and a middle word that takes one 1-bit pass.  The last lines are the coverage summary: one line per feature the sweep
 means to reach, with the number of cases that reached it; a zero there, like a mismatch, is exit status 1."""
-import collections
 import os
 import sys
 import traceback
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-
-from pandrs_amd import _lib as L  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fuzz_common import DRY, DRY_MODE, DT_NAME, SPACES, L, Mismatch, bits, check, cov, first_diff_any, np, place, to_np  # noqa: E402,F401
 from tests import window_ref as WR  # noqa: E402
 from tests.helpers import filter_ref  # noqa: E402
 from tests.sort_ref import STRINGS, Col, rank_of, ref_cmp, ref_lexsort  # noqa: E402
+import fuzz_chain2  # noqa: E402
+import fuzz_columns  # noqa: E402
 
-DRY = os.environ.get("FUZZ_DRY", "0") == "1"
-KINDS = ("sort", "filter", "window", "chain")
-KIND = os.environ.get("FUZZ_KIND", "")
-assert KIND in ("",) + KINDS, KIND
-
-SPACES = ("host", "device", "device_offset", "resident")
-DT_NAME = {L.I64: "i64", L.F64: "f64", L.U32CODE: "str", L.BOOLBITS: "bool"}
-NP_OF = {L.I64: np.int64, L.F64: np.float64, L.U32CODE: np.uint32}
+OLD_KINDS = ("sort", "filter", "window", "chain")
 OPS = {"sum": L.WINDOW_SUM, "mean": L.WINDOW_MEAN, "var": L.WINDOW_VAR, "std": L.WINDOW_STD, "min": L.WINDOW_MIN,
        "max": L.WINDOW_MAX, "count": L.WINDOW_COUNT}
 WKINDS = {"rolling": L.WINDOW_KIND_ROLLING, "expanding": L.WINDOW_KIND_EXPANDING, "ewm": L.WINDOW_KIND_EWM}
 CHAINS = ("filter_sort_window", "filter_groupby", "sort_clustered_groupby", "sort_window")
 SIGN = np.uint64(1 << 63)
-cov = collections.Counter()
-
-
-def bits(a):
-    return np.packbits(np.asarray(a, bool), bitorder="little")
-
-
-class Mismatch(AssertionError):
-    pass
-
-
-def check(ok, what, detail=None):
-    if not ok:
-        raise Mismatch("%s%s" % (what, "" if detail is None else ": %s" % (detail,)))
-
-
-def first_diff_any(got, want):
-    """First differing position of two arrays compared by their bytes (floats through window_ref.first_diff)."""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape:
-        return ("shape", got.shape, want.shape)
-    if got.dtype == np.float64 and want.dtype == np.float64:
-        gi, wi = got.view(np.int64), want.view(np.int64)
-    else:
-        gi, wi = got, want
-    bad = np.flatnonzero(gi != wi)
-    return None if not len(bad) else (int(bad[0]), got[bad[0]].item(), want[bad[0]].item())
-
-
-# ---- placing a column in a memory space -----------------------------------------------------------------------------
-def place(ctx, space, data, mask, dtype, n, keep):
-    """(data, mask, dtype) host arrays -> what the engine takes, in `space`.  device_offset: the data 8 bytes into its
-    allocation (8-byte aligned, not 256), the mask 3 bytes into its own (odd)."""
-    if space == "host":
-        return (data, mask, dtype)
-    if space == "resident":
-        r = ctx.upload_column_n(data, mask, dtype, n)
-        keep.append(r)
-        return r
-    import torch
-    def dev(a, lead):
-        a = np.ascontiguousarray(a)
-        t = torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a)
-        if not lead:
-            return t.to("cuda:0")
-        buf = torch.zeros(len(t) + lead + 3, dtype=t.dtype, device="cuda:0")
-        buf[lead:lead + len(t)] = t.to("cuda:0")
-        return buf[lead:lead + len(t)]
-    off = space == "device_offset"
-    d = dev(data, (8 // data.dtype.itemsize) if off else 0)
-    m = None if mask is None else dev(mask, 3 if off else 0)
-    return (d, m, dtype)
-
-
-def to_np(a):
-    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
 # ---- sort: key makers ---------------------------------------------------------------------------------------------------
@@ -782,10 +720,19 @@ def desc_chain(d):
 
 
 # ---- the sweep ---------------------------------------------------------------------------------------------------------------
-DRAW = {"sort": (draw_sort, classify_sort, run_sort, desc_sort, SORT_FEATURES),
-        "filter": (draw_filter, classify_filter, run_filter, desc_filter, FILTER_FEATURES),
-        "window": (draw_window, classify_window, run_window, desc_window, WINDOW_FEATURES),
-        "chain": (draw_chain, classify_chain, run_chain, desc_chain, CHAIN_FEATURES)}
+# kind -> (draw, classify, run, desc, features, expect).  expect (the column ops' kinds and chain2) computes every reference
+# result of a drawn case without the engine: what FUZZ_DRY=2 runs, and what run() compares the device with.
+DRAW = {"sort": (draw_sort, classify_sort, run_sort, desc_sort, SORT_FEATURES, None),
+        "filter": (draw_filter, classify_filter, run_filter, desc_filter, FILTER_FEATURES, None),
+        "window": (draw_window, classify_window, run_window, desc_window, WINDOW_FEATURES, None),
+        "chain": (draw_chain, classify_chain, run_chain, desc_chain, CHAIN_FEATURES, None)}
+DRAW.update(fuzz_columns.KINDS)
+DRAW.update(fuzz_chain2.KINDS)
+KINDS = tuple(DRAW)
+# With FUZZ_KIND unset: the four older kinds keep their shares of one half, the nine newer ones share the other.
+KIND_P = [0.2, 0.1, 0.15, 0.05] + [0.5 / (len(KINDS) - 4)] * (len(KINDS) - 4)
+KIND = os.environ.get("FUZZ_KIND", "")
+assert KIND in ("",) + KINDS, KIND
 
 
 def main():
@@ -802,17 +749,21 @@ def main():
     fails = 0
     for case in range(first_case, n_cases):
         rng = np.random.default_rng(seed0 * 100003 + case)
-        kind = KIND or KINDS[int(rng.choice(4, p=[0.4, 0.2, 0.3, 0.1]))]
-        draw, classify, run, desc, _ = DRAW[kind]
+        kind = KIND or KINDS[int(rng.choice(len(KINDS), p=KIND_P))]
+        draw, classify, run, desc, _, expect = DRAW[kind]
         d = text = None
         try:
             d = draw(rng, case)
             text = desc(d)
-            for f in set(classify(d)):
-                cov[f] += 1
+            feats = set(classify(d))
+            if DRY_MODE == 2 and expect is not None:
+                expect(d)
             if not DRY:
                 run(ctx, d)
                 text = desc(d)
+                feats -= set(d.get("uncount", ())) if isinstance(d, dict) else set()
+            for f in feats:
+                cov[f] += 1
             print("ok   %3d %s" % (case, text), flush=True)
         except Exception:
             fails += 1
@@ -822,14 +773,15 @@ def main():
     if ctx is not None:
         ctx.close()
     wanted = [f for k in ((KIND,) if KIND else KINDS) for f in DRAW[k][4]]
-    print("coverage (%s):" % ("dry run: drawn and classified, no engine call" if DRY else "cases run"))
+    print("coverage (%s):" % ("cases run" if not DRY else "dry run: drawn and classified, no engine call" if DRY_MODE == 1 else
+                              "dry run: drawn, classified and every reference result computed, no engine call"))
     for f in wanted:
         print("  %-46s %d" % (f, cov[f]))
     missed = [f for f in wanted if cov[f] == 0]
     if missed:
         print("coverage: %d features not reached: %s" % (len(missed), missed))
     print("fuzz_ops done: %d cases, %d failures" % (n_cases - first_case, fails), flush=True)
-    sys.exit(1 if fails or (missed and not first_case) else 0)
+    sys.exit(1 if fails or (missed and not first_case and DRY_MODE != 2) else 0)      # FUZZ_DRY=2 caps the row counts
 
 
 if __name__ == "__main__":

@@ -20,6 +20,7 @@ LAG_OPS = [SHIFT, DIFF, PCT_CHANGE]
 CANON_NAN = np.uint64(0x7FF8000000000000)
 NAN = CANON_NAN.view(np.float64)
 U = 2.0 ** -53
+TINY = 2.2250738585072014e-308                                  # the smallest normal f64
 
 
 def bits(flags):
@@ -58,6 +59,32 @@ def sum_bound(x, nulls=None):
     """2 gamma_k sum_{j<=i} |x_j| per row, k the non-null rows in 0 .. i (pandrs_hip.h)"""
     v, nl = as_f64(x), _nulls(x, nulls)
     return 2.0 * gamma(np.cumsum(~nl)) * np.cumsum(np.where(nl, 0.0, np.abs(v)))
+
+
+def compare_cells(op, got, want, x, nulls, exact):
+    """One fold's cells against the twin's, by the contract of its op (pandrs_hip.h): MAX, MIN and COUNT bit for bit, as is a SUM
+    the caller knows to be exact; SUM within sum_bound; PROD within 2 gamma_k where the twin's product is normal, the same
+    sign, infinity and zero elsewhere.  The rule of tests/test_gpu_cumulative.py and of the randomised sweep."""
+    if op in (MAX, MIN, COUNT) or (op == SUM and exact):
+        assert same_bits(got, want), (op, np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))[:5])
+        return
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), (op, np.flatnonzero(np.isnan(got) != nan)[:5])
+    k = np.cumsum(np.ones(len(want), bool) if nulls is None else ~np.asarray(nulls, bool))
+    with np.errstate(all="ignore"):
+        if op == SUM:
+            fin = np.isfinite(want)
+            err, bound = np.abs(got[fin] - want[fin]), sum_bound(x, nulls)[fin]
+            assert np.all(err <= bound), (np.flatnonzero(err > bound)[:5], float(np.max(err / np.maximum(bound, TINY))))
+            assert same_bits(got[~fin & ~nan], want[~fin & ~nan])
+        else:
+            normal = np.isfinite(want) & (np.abs(want) >= TINY)
+            rel = np.abs(got[normal] / want[normal] - 1.0)
+            assert np.all(rel <= 2 * gamma(k[normal])), (np.flatnonzero(rel > 2 * gamma(k[normal]))[:5], float(rel.max()))
+            rest = ~normal & ~nan
+            assert np.array_equal(np.signbit(got[rest]), np.signbit(want[rest])) and np.array_equal(np.isinf(got[rest]), np.isinf(want[rest]))
+            zero = rest & (want == 0.0)
+            assert np.all(got[zero] == 0.0)
 
 
 # ---- f64::max / f64::min with the signed-zero convention of pandrs_hip_window: -0.0 below +0.0 --------------------------------

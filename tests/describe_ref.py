@@ -64,3 +64,47 @@ def describe_ref(values, nulls, dtype):
         std = np.sqrt(variance)
     return {"count": n, "mean": mean, "std": std, "min": s[0], "25%": percentile_ref(s, 25.0), "50%": percentile_ref(s, 50.0),
             "75%": percentile_ref(s, 75.0), "max": s[-1], "sorted": s}
+
+
+# ---- the comparison rule of tests/test_gpu_describe.py and of the randomised sweep ---------------------------------------------
+FIELD = {"min": "min", "25%": "q1", "50%": "median", "75%": "q3", "max": "max"}     # describe_ref's key -> pandrs_hip_describe_stats'
+
+
+def same(a, b):
+    a, b = np.float64(a), np.float64(b)
+    return bool((np.isnan(a) and np.isnan(b)) or a == b)
+
+
+def compare_describe(got, values, nulls, dtype, moments=True):
+    """Context.describe's dict against describe_ref: the count, and min, max and the quartiles as equal values (a zero may differ
+    in its sign, pandrs_hip.h); with `moments` the mean within 1e-9 of the mean magnitude and std within 1e-9 relative."""
+    s, rows = sorted_cells(values, nulls, dtype)
+    n = np.asarray(values).shape[0]
+    assert got["count"] == s.shape[0], (got["count"], s.shape[0])
+    if s.shape[0] == 0:
+        assert all(np.isnan(got[f]) for f in ("mean", "std", "min", "q1", "median", "q3", "max")), got
+        return
+    want = describe_ref(values, nulls, dtype)
+    for k, f in FIELD.items():
+        assert same(got[f], want[k]), (k, got[f], want[k], n)
+    if moments:
+        if np.isnan(want["mean"]):
+            assert np.isnan(got["mean"])
+        else:
+            assert abs(got["mean"] - want["mean"]) <= 1e-9 * np.abs(rows).sum() / len(rows), (got["mean"], want["mean"])
+        if np.isnan(want["std"]):
+            assert np.isnan(got["std"])
+        else:
+            assert abs(got["std"] - want["std"]) <= 1e-9 * want["std"], (got["std"], want["std"])
+
+
+def compare_quantiles(q, count, values, nulls, dtype, ps):
+    """Context.quantiles' (values, count) against percentile_ref over the sorted cells: equal values, NaN without a cell."""
+    s, _ = sorted_cells(values, nulls, dtype)
+    n = np.asarray(values).shape[0]
+    assert count == s.shape[0] and len(q) == len(ps), (count, s.shape[0], len(q), len(ps))
+    if s.shape[0] == 0:
+        assert np.isnan(q).all(), q
+        return
+    for p, v in zip(ps, q):
+        assert same(v, percentile_ref(s, p)), (p, v, percentile_ref(s, p), n)

@@ -18,13 +18,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 from pandrs_amd import _lib as L  # noqa: E402
-from tests.cumulative_ref import (COUNT, CUM_OPS, DIFF, LAG_OPS, MAX, MIN, NAN, PCT_CHANGE, PROD, SHIFT, SUM, bits, cum_loop, cum_twin, gamma,  # noqa: E402
-                                  lag_loop, lag_twin, same_bits, sum_bound)
+from tests.cumulative_ref import (COUNT, CUM_OPS, DIFF, LAG_OPS, MAX, MIN, NAN, PCT_CHANGE, PROD, SHIFT, SUM, TINY, bits, compare_cells,  # noqa: E402
+                                  cum_loop, cum_twin, lag_loop, lag_twin, same_bits)
 
 HEADER = open(os.path.join(ROOT, "include", "pandrs_hip.h")).read()
 T = int(re.search(r"cum_tile_rows = (\d+)", HEADER).group(1))
 PER_CU = int(re.search(r"cum_blocks_per_cu = (\d+)", HEADER).group(1))
-TINY = 2.2250738585072014e-308                                  # the smallest normal f64
 
 
 @pytest.fixture(scope="module")
@@ -54,30 +53,6 @@ def host(vals, mask, n):
     return vals, mask, flags
 
 
-def compare(op, got, want, x, nulls, exact):
-    """One fold's cells against the twin's, by the contract of its op."""
-    if op in (MAX, MIN, COUNT) or (op == SUM and exact):
-        assert same_bits(got, want), (op, np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))[:5])
-        return
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), (op, np.flatnonzero(np.isnan(got) != nan)[:5])
-    k = np.cumsum(np.ones(len(want), bool) if nulls is None else ~np.asarray(nulls, bool))
-    with np.errstate(all="ignore"):
-        if op == SUM:
-            fin = np.isfinite(want)
-            err, bound = np.abs(got[fin] - want[fin]), sum_bound(x, nulls)[fin]
-            assert np.all(err <= bound), (np.flatnonzero(err > bound)[:5], float(np.max(err / np.maximum(bound, TINY))))
-            assert same_bits(got[~fin & ~nan], want[~fin & ~nan])
-        else:
-            normal = np.isfinite(want) & (np.abs(want) >= TINY)
-            rel = np.abs(got[normal] / want[normal] - 1.0)
-            assert np.all(rel <= 2 * gamma(k[normal])), (np.flatnonzero(rel > 2 * gamma(k[normal]))[:5], float(rel.max()))
-            rest = ~normal & ~nan
-            assert np.array_equal(np.signbit(got[rest]), np.signbit(want[rest])) and np.array_equal(np.isinf(got[rest]), np.isinf(want[rest]))
-            zero = rest & (want == 0.0)
-            assert np.all(got[zero] == 0.0)
-
-
 def check_cum(ctx, x, nulls=None, ops=CUM_OPS, col=None, exact=False, wants=None, **kw):
     """One column under `ops` against the vectorised restatement: the cells, the mask, the count, and `mask is None` exactly
     when no bit is set; `col` overrides how the column is passed, `wants` carries twins computed before."""
@@ -92,7 +67,7 @@ def check_cum(ctx, x, nulls=None, ops=CUM_OPS, col=None, exact=False, wants=None
         vals, mask, n_null = ctx.cumulative(col, n, op, **kw)
         vals, mask, flags = host(vals, mask, n)
         assert vals.dtype == want.dtype
-        compare(op, vals, want, x, nulls, exact)
+        compare_cells(op, vals, want, x, nulls, exact)
         assert n_null == int(gone.sum()) and (mask is None) == (n_null == 0), (op, n_null, int(gone.sum()))
         assert np.array_equal(flags, gone), op
     return wants
@@ -223,7 +198,7 @@ def test_sum_of_real_data_stays_inside_the_derived_bound(ctx, grid):
         dropped = cum_twin(x, None, SUM)[0]                                # the bound would catch a dropped tile carry
         dropped[T:] -= dropped[T - 1]
         with pytest.raises(AssertionError):
-            compare(SUM, dropped, cum_twin(x, None, SUM)[0], x, None, False)
+            compare_cells(SUM, dropped, cum_twin(x, None, SUM)[0], x, None, False)
 
 
 def test_sum_nan_inf_and_negative_zero(ctx, grid):
@@ -519,7 +494,7 @@ def test_frame_methods_against_the_twins(ctx):
             got = call(name)
             want, _ = cum_twin(data, nulls, op)
             assert isinstance(got, list) and all(type(v) is (int if op == COUNT else float) for v in got)
-            compare(op, np.array(got, want.dtype), want, data, nulls, op == SUM)
+            compare_cells(op, np.array(got, want.dtype), want, data, nulls, op == SUM)
         for periods in (1, -2, n + 3):
             got = df.shift(name, periods)
             want, gone = lag_twin(data, nulls, SHIFT, periods)

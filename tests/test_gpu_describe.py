@@ -18,10 +18,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 from pandrs_amd import _lib as L  # noqa: E402
-from tests.describe_ref import describe_ref, percentile_ref, sorted_cells  # noqa: E402
+from tests.describe_ref import FIELD, compare_describe, compare_quantiles, describe_ref, percentile_ref, same  # noqa: E402
 
 PS = [0.0, 5.0, 10.0, 25.0, 50.0, 75.0, 90.0, 95.0, 100.0]
-FIELD = {"min": "min", "25%": "q1", "50%": "median", "75%": "q3", "max": "max"}
 
 
 @pytest.fixture(scope="module")
@@ -47,11 +46,6 @@ def bits(a):
     return np.packbits(np.asarray(a, bool), bitorder="little")
 
 
-def same(a, b):
-    a, b = np.float64(a), np.float64(b)
-    return bool((np.isnan(a) and np.isnan(b)) or a == b)
-
-
 def check(ctx, x, nulls=None, dtype=L.F64, moments=True, col=None, ps=PS):
     """describe and quantiles of one column against the reference restatement; `col` overrides how the column is passed."""
     npdt = np.int64 if dtype == L.I64 else np.float64
@@ -60,25 +54,9 @@ def check(ctx, x, nulls=None, dtype=L.F64, moments=True, col=None, ps=PS):
     col = col if col is not None else (x, None if nulls is None else bits(nulls), dtype)
     got = ctx.describe(col, n)
     q, cnt = ctx.quantiles(col, n, ps)
-    s, rows = sorted_cells(x, nulls, npdt)
-    assert got["count"] == cnt == s.shape[0]
-    if s.shape[0] == 0:
-        assert all(np.isnan(got[f]) for f in ("mean", "std", "min", "q1", "median", "q3", "max")) and np.isnan(q).all()
-        return got
-    want = describe_ref(x, nulls, npdt)
-    for k, f in FIELD.items():
-        assert same(got[f], want[k]), (k, got[f], want[k], n)
-    for p, v in zip(ps, q):
-        assert same(v, percentile_ref(s, p)), (p, v, percentile_ref(s, p), n)
-    if moments:
-        if np.isnan(want["mean"]):
-            assert np.isnan(got["mean"])
-        else:
-            assert abs(got["mean"] - want["mean"]) <= 1e-9 * np.abs(rows).sum() / len(rows), (got["mean"], want["mean"])
-        if np.isnan(want["std"]):
-            assert np.isnan(got["std"])
-        else:
-            assert abs(got["std"] - want["std"]) <= 1e-9 * want["std"], (got["std"], want["std"])
+    assert got["count"] == cnt
+    compare_describe(got, x, nulls, npdt, moments)
+    compare_quantiles(q, cnt, x, nulls, npdt, ps)
     return got
 
 

@@ -32,6 +32,7 @@ from oracle import oracle as O  # noqa: E402
 from pandrs_amd import _lib as L  # noqa: E402
 from tests import join_ref as J  # noqa: E402
 from tests import test_gpu_cumulative as TC  # noqa: E402
+from tests import describe_ref as DREF  # noqa: E402
 from tests import test_gpu_describe as TD  # noqa: E402
 from tests import test_gpu_fill as TF  # noqa: E402
 from tests import test_gpu_filter as TFI  # noqa: E402
@@ -150,7 +151,7 @@ def memo(fn):
 def shared_references(monkeypatch):
     """The checkers of the op modules restate their reference on every call; here one input is checked up to a dozen times."""
     for mod, names in ((TK, ("topk_ref", "idx_extreme_ref")), (TR, ("rank_ref_all",)), (TF, ("fill_twin",)), (TC, ("cum_twin", "lag_twin")),
-                       (TD, ("sorted_cells", "describe_ref"))):
+                       (DREF, ("sorted_cells", "describe_ref"))):         # (test_gpu_describe.check compares through tests/describe_ref.py)
         for name in names:
             monkeypatch.setattr(mod, name, memo(getattr(mod, name)))
 

@@ -2,7 +2,7 @@
 here without a GPU against independent, deliberately naive restatements: a per-row Python loop over each window, a closed
 form in exact rational arithmetic, a comparator sort.  Every comparison but the EWM one is bit for bit.  Also: the
 generator of experiments/fuzz_ops.py, run dry (no engine call), reaches every feature it means to reach at the seeds and
-case counts tests/test_gpu_fuzz.py uses."""
+case counts tests/test_gpu_fuzz.py uses, and the twins of the newer kinds take every case their generators draw."""
 import os
 import subprocess
 import sys
@@ -228,3 +228,22 @@ def test_fuzz_ops_dry_run_reaches_every_feature(kind):
     lines = r.stdout[r.stdout.index("coverage ("):].splitlines()[1:-1]
     assert len(lines) >= 5 and all(line.startswith("  %s." % kind) for line in lines), tail
     assert all(int(line.split()[-1]) > 0 for line in lines), tail
+
+
+# FUZZ_DRY=2: the generators and the twins alone - every reference result of a drawn case is computed, no engine call - so a
+# generator that draws what its twin cannot take, or a chain stage whose reference breaks on the stage before, fails here.
+NEW_KINDS = ("describe", "rank", "fill", "topk", "predicate", "wquant", "cum", "eval", "chain2")
+
+
+@pytest.mark.parametrize("kind", NEW_KINDS)
+def test_fuzz_ops_references_take_every_draw(kind):
+    assert kind in FUZZ_OPS_SLICES
+    count, seed = FUZZ_OPS_SLICES[kind]
+    count = count if kind == "chain2" else min(count, 40)
+    env = dict(os.environ, FUZZ_DRY="2", FUZZ_KIND=kind)
+    env.pop("FUZZ_FIRST", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "experiments", "fuzz_ops.py"), str(count), str(seed)], capture_output=True,
+                       text=True, timeout=280, env=env, cwd=ROOT)
+    tail = "\n".join((r.stdout + r.stderr).splitlines()[-60:])
+    assert r.returncode == 0, tail
+    assert "fuzz_ops done: %d cases, 0 failures" % count in r.stdout and r.stdout.count("\nok ") + r.stdout.startswith("ok ") == count, tail
