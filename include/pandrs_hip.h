@@ -1003,8 +1003,8 @@ int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip
  * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
  * col / out_data, an op outside its enum, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK,
  * nothing written, *out_n_null = 0.
- * Out of scope: group-wise cumulative ops, clip, skipna= and reverse scans, String and Boolean columns, the legacy string frame,
- * TimeSeries::{diff,shift,pct_change}. */
+ * Out of scope: clip, skipna= and reverse scans, String and Boolean columns, the legacy string frame,
+ * TimeSeries::{diff,shift,pct_change}.  The group-wise cumulative ops are pandrs_hip_grouped, below. */
 typedef enum pandrs_hip_cum_op {
     PANDRS_HIP_CUM_SUM = 0, PANDRS_HIP_CUM_PROD = 1, PANDRS_HIP_CUM_MAX = 2, PANDRS_HIP_CUM_MIN = 3, PANDRS_HIP_CUM_COUNT = 4
 } pandrs_hip_cum_op;
@@ -1018,6 +1018,67 @@ int32_t pandrs_hip_cumulative(pandrs_hip_ctx *ctx, int32_t mem_space, const pand
 
 int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
                        int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
+
+/* ---- the same folds and lags within groups: GroupBy cumsum, cummax, cummin, cumcount, row_number, shift, diff, pct_change ------------
+ * The reference's GroupWise*Ops (src/dataframe/groupby_window.rs) are marked "simplified implementation" and ignore the group
+ * columns, so the semantics are this header's own: a grouped op gives, for every group, the result of the ungrouped op on that
+ * group's rows in ascending row order, written back at those rows' positions.
+ * Which groups: the ones the context retains from its last successful pandrs_hip_groupby_indices (rows, offsets, n_groups,
+ * n_rows).  One grouping serves any number of grouped calls; the keys are whatever that call took (any dtype, several keys, NULL
+ * keys as one group per distinct combination).  No retained grouping, or n_rows different from the grouping's:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT, and the message says which.  A grouped call takes its scratch from the work arena and leaves
+ * the retained grouping as it was.
+ * Within group g, with rows r_0 < r_1 < ..., row r_t answers:
+ *   CUM_SUM / CUM_MAX / CUM_MIN / CUM_COUNT   pandrs_hip_cumulative's contract over r_0 .. r_t.  SUM folds from +0.0 (a group of
+ *          only -0.0 gives +0.0; a NaN or +-inf cell affects later rows of its own group only).  MAX / MIN fold from -inf /
+ *          +inf, skip NaN cells, hold -0.0 below +0.0, bit for bit.  COUNT is I64: the rows so far in the group that are neither
+ *          null nor NaN.  A row under a null bit answers NaN with its output bit set and the running value passes through; COUNT
+ *          writes the running count there and sets no bit.  SUM's accuracy: |got - ref| <= 2 gamma_k sum|x|, k and the sum over
+ *          the group's own prefix, wherever that running sum of |x| stays finite; integer-valued data with sum|x| below 2^53 per
+ *          group: bit for bit.  A group's prefix is folded from its own cells only: it is never a global prefix minus the prefix
+ *          at the group's start, which would cancel across groups.
+ *   ROW_NUMBER   I64, the value t.  Every row counts, null or not; col may be NULL and is not read; no null bit is set.
+ *   SHIFT / DIFF / PCT_CHANGE   pandrs_hip_lag's contract with "row i - periods" read as r_{t - periods} of the same group; a
+ *          source position outside the group is treated like a source row before row 0.  SHIFT takes either sign of periods;
+ *          DIFF / PCT_CHANGE with periods < 0: PANDRS_HIP_ERR_INVALID_ARGUMENT.  Bit for bit, every operation rounded on its own
+ *          (no fused multiply-add); a NaN that SHIFT copies arrives canonical (0x7FF8000000000000).
+ * The output is F64 for every op except CUM_COUNT and ROW_NUMBER, which write I64.  periods is read by the three lag ops only.
+ * How (grouped.hip): the work runs in sorted-position order (position j holds row rows[j]; a group is the contiguous positions
+ * offsets[g] .. offsets[g + 1]).  Group heads are bit words, one bit per position, set from offsets by atomic ORs (one per word and wave).
+ * The folds are a segmented reduce-then-apply over contiguous spans of whole tiles, the operator on (head seen, value) pairs:
+ * kernel 1 gathers the column through rows[] once, leaves the cells and their null bits (as ballot words) contiguous in the
+ * workspace and folds each span into a summary (does it hold a head; the fold of the cells after its last head); the prologue of
+ * kernel 2 folds the summaries of earlier spans back to the nearest span that holds a head, then scans its tiles with a
+ * cross-lane scan driven by the head word and scatters out[rows[j]].  Lag and ROW_NUMBER take the group's first position per
+ * position from one ordinary max-scan of the head positions (the same tile scan) into a 32-bit array; j' = j - periods is in
+ * the group iff 0 <= j' < n_rows and start[j'] == start[j]; lag reads the gathered cells, so the column is gathered once there
+ * too.  Every hand-off between workgroups is a kernel boundary; no workgroup waits for another; no kernel uses scratch.
+ * The output mask of a fold is the input mask with the bits past n_rows cleared (a copy, no scatter), all zero for COUNT and
+ * ROW_NUMBER; lag builds it in a zeroed, aligned workspace bitmap with atomic ORs on 32-bit words and stores it bytewise.
+ * Geometry (tests read it): grouped_tile_rows = 2048 positions, grouped_blocks_per_cu = 4, grid = min(grouped_blocks_per_cu x
+ * compute units, ceil(n_rows / grouped_tile_rows)) workgroups; span b holds tiles / grid tiles and one more when b < tiles % grid.
+ * Buffers and errors as pandrs_hip_cumulative: col is I64 or F64, any other dtype PANDRS_HIP_ERR_TYPE_MISMATCH; host columns and
+ * outputs are staged, device and resident columns are read in place; data and out_data are 8-byte aligned, the masks may sit at
+ * any byte offset, input bits past n_rows are ignored; out_null_mask receives exactly ceil(n_rows / 8) bytes stored bytewise, no
+ * byte beyond touched, and may be NULL; an output overlapping the column in the same memory space:
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT; out_n_null is a host pointer and may be NULL.  n_rows == 0 (with a retained grouping of 0
+ * rows): OK, nothing written.  ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold:
+ * PANDRS_HIP_ERR_BELOW_THRESHOLD; an op outside the enum: PANDRS_HIP_ERR_INVALID_ARGUMENT.  The row limit is the grouping's:
+ * fewer than 2^32 - 16384 rows.
+ * Workspace, sized up front in one arena, in bytes per row: 8 for the gathered cells (not ROW_NUMBER), 4 for the group starts
+ * (lag and ROW_NUMBER), 2/8 for the head and null words, 1/8 for the lag bitmap; plus 12 bytes per workgroup of the full grid and
+ * the counter.  Staging: a host column and host outputs.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * pandrs_hip_get_timings: the phase is PANDRS_HIP_PHASE_AGGREGATE, n_partitions is 0, algorithmic_bytes counts the streams run.
+ * Out of scope: a grouped PROD (the sticky range-excursion rewrite of pandrs_hip_cumulative has no obvious per-group form),
+ * group-wise fills, a grouped rank, a grouped top-k and group-wise windows, String and Boolean columns. */
+typedef enum pandrs_hip_grouped_op {
+    PANDRS_HIP_GROUPED_CUM_SUM = 0, PANDRS_HIP_GROUPED_CUM_MAX = 1, PANDRS_HIP_GROUPED_CUM_MIN = 2,
+    PANDRS_HIP_GROUPED_CUM_COUNT = 3, PANDRS_HIP_GROUPED_ROW_NUMBER = 4,
+    PANDRS_HIP_GROUPED_SHIFT = 5, PANDRS_HIP_GROUPED_DIFF = 6, PANDRS_HIP_GROUPED_PCT_CHANGE = 7
+} pandrs_hip_grouped_op;
+
+int32_t pandrs_hip_grouped(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
+                           int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
 
 /* ---- derived columns: one postfix program over up to eight columns, evaluated per row in one stream -----------------------------
  * What the predicate and cumulative blocks above leave out (combining masks, predicates between two columns, where_cond / mask /

@@ -1278,6 +1278,33 @@ public:
     OptimizedDataFrame last(const std::string &c) const { return agg({{c, AggregateOp::Last}}); }
     OptimizedDataFrame nunique(const std::string &c) const { return agg({{c, AggregateOp::Nunique}}); }   // legacy GroupBy::nunique (src/dataframe/groupby.rs:386-393)
 
+    // cumsum / cummax / cummin / cumcount / row_number / shift / diff / pct_change within the groups (pandrs_hip_grouped): for
+    // every group the frame-level method of the same name over the group's rows in ascending row order, written at those rows;
+    // vectors aligned with the frame's rows.  No closure and no sub-frames: one pandrs_hip_groupby_indices and one
+    // pandrs_hip_grouped call each (this mirror regroups per call).  Errors before any device call: ColumnNotFound, Type (a
+    // String or Boolean column); an empty frame gives empty vectors.
+    std::vector<double> cumsum(const std::string &c) const { return grouped<double>(&c, PANDRS_HIP_GROUPED_CUM_SUM, 0, nullptr); }
+    std::vector<double> cummax(const std::string &c) const { return grouped<double>(&c, PANDRS_HIP_GROUPED_CUM_MAX, 0, nullptr); }
+    std::vector<double> cummin(const std::string &c) const { return grouped<double>(&c, PANDRS_HIP_GROUPED_CUM_MIN, 0, nullptr); }
+    std::vector<size_t> cumcount(const std::string &c) const {
+        const std::vector<int64_t> v = grouped<int64_t>(&c, PANDRS_HIP_GROUPED_CUM_COUNT, 0, nullptr);
+        return std::vector<size_t>(v.begin(), v.end());
+    }
+    std::vector<size_t> row_number() const {
+        const std::vector<int64_t> v = grouped<int64_t>(nullptr, PANDRS_HIP_GROUPED_ROW_NUMBER, 0, nullptr);
+        return std::vector<size_t>(v.begin(), v.end());
+    }
+    std::vector<std::optional<double>> shift(const std::string &c, int32_t periods) const {
+        std::vector<uint8_t> mask;
+        const std::vector<double> v = grouped<double>(&c, PANDRS_HIP_GROUPED_SHIFT, periods, &mask);
+        std::vector<std::optional<double>> out(v.size());
+        for (size_t i = 0; i < v.size(); i++)
+            if (!detail::bit_at(mask, i)) out[i] = v[i];
+        return out;
+    }
+    std::vector<double> diff(const std::string &c, size_t periods) const { return grouped<double>(&c, PANDRS_HIP_GROUPED_DIFF, (int64_t)std::min(periods, df.row_count()), nullptr); }
+    std::vector<double> pct_change(const std::string &c, size_t periods) const { return grouped<double>(&c, PANDRS_HIP_GROUPED_PCT_CHANGE, (int64_t)std::min(periods, df.row_count()), nullptr); }
+
     // the pub field `groups` (types.rs:52): HashMap<Vec<String>, Vec<usize>>, every list ascending
     std::map<std::vector<std::string>, std::vector<size_t>> groups(const char *null_string = "NULL") const {
         std::vector<pandrs_hip_column> keys;
@@ -1374,6 +1401,28 @@ public:
     static std::string op_name(AggregateOp op) {
         static const char *names[] = {"sum", "mean", "min", "max", "count", "std", "var", "median", "first", "last", "custom", "nunique"};
         return names[(int)op];
+    }
+
+private:
+    // the grouping, then one pandrs_hip_grouped call (op = pandrs_hip_grouped_op; column == nullptr: ROW_NUMBER) -> its cells
+    // (T = int64_t for CUM_COUNT and ROW_NUMBER, double otherwise), and the null bitmap when `mask` is given
+    template <typename T>
+    std::vector<T> grouped(const std::string *column, int32_t op, int64_t periods, std::vector<uint8_t> *mask) const {
+        if (column && df.column(*column).index() > 1) throw Error(Error::Type, "Column '" + *column + "' is not a numeric type");
+        const size_t n = df.row_count();
+        std::vector<T> out(n);
+        if (mask) mask->assign((n + 7) / 8, 0);
+        if (n) {
+            std::vector<pandrs_hip_column> keys;
+            for (auto &k : group_by_columns) keys.push_back(df.view_of(k));
+            int64_t g = 0;
+            detail::check(pandrs_hip_groupby_indices(detail::context(), df.mem_space(), keys.data(), (int32_t)keys.size(), (int64_t)n, &g));
+            pandrs_hip_column v{};
+            if (column) v = df.view_of(*column);
+            detail::check(pandrs_hip_grouped(detail::context(), df.mem_space(), column ? &v : nullptr, (int64_t)n, op, periods, PANDRS_HIP_MEM_HOST,
+                                             out.data(), mask ? mask->data() : nullptr, nullptr));
+        }
+        return out;
     }
 };
 

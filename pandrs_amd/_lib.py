@@ -27,6 +27,8 @@ FILL_FFILL, FILL_BFILL, FILL_LINEAR, FILL_VALUE = range(4)
 TOPK_LARGEST, TOPK_SMALLEST = range(2)
 CUM_SUM, CUM_PROD, CUM_MAX, CUM_MIN, CUM_COUNT = range(5)
 LAG_SHIFT, LAG_DIFF, LAG_PCT_CHANGE = range(3)
+GROUPED_CUM_SUM, GROUPED_CUM_MAX, GROUPED_CUM_MIN, GROUPED_CUM_COUNT, GROUPED_ROW_NUMBER, GROUPED_SHIFT, GROUPED_DIFF, \
+    GROUPED_PCT_CHANGE = range(8)
 PRED_GT, PRED_GE, PRED_LT, PRED_LE, PRED_EQ, PRED_NE, PRED_BETWEEN, PRED_BETWEEN_EXCLUSIVE, PRED_ISNA, PRED_NOTNA, PRED_IS_FINITE, \
     PRED_IS_INFINITE = range(12)
 EVAL_COL, EVAL_CONST, EVAL_ADD, EVAL_SUB, EVAL_MUL, EVAL_DIV, EVAL_REM, EVAL_MAX, EVAL_MIN, EVAL_NEG, EVAL_ABS, EVAL_FLOOR, EVAL_CEIL, \
@@ -174,6 +176,8 @@ SYMBOLS = {
     "pandrs_hip_cumulative": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
     "pandrs_hip_lag": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P,
                                    C.POINTER(C.c_int64)]),
+    "pandrs_hip_grouped": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P,
+                                       C.POINTER(C.c_int64)]),
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -578,6 +578,13 @@ int32_t pandrs_hip_lag(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_
     return pandrs::lag_entry(ctx, mem_space, col, n_rows, op, periods, out_mem_space, out_data, out_null_mask, out_n_null);
 } catch (...) { return pandrs::on_exception("pandrs_hip_lag"); }
 
+int32_t pandrs_hip_grouped(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op,
+                           int64_t periods, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "grouped: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::grouped_entry(ctx, mem_space, col, n_rows, op, periods, out_mem_space, out_data, out_null_mask, out_n_null);
+} catch (...) { return pandrs::on_exception("pandrs_hip_grouped"); }
+
 int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
                         const int32_t *ops, const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,
                         int64_t *out_count) try {

@@ -432,6 +432,9 @@ int32_t cumulative_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_
                          void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
 int32_t lag_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, int64_t periods,
                   int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
+// grouped.hip: the same folds and lags (op = pandrs_hip_grouped_op) within the groups c->gr retains
+int32_t grouped_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t op, int64_t periods,
+                      int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_n_null);
 // eval.hip: one postfix program (ops = pandrs_hip_eval_op) over up to eight columns -> one F64 column or one row mask
 int32_t eval_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows, const int32_t *ops,
                    const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask, int64_t *out_count);

@@ -18,7 +18,7 @@
 // cumprod scans (mantissa, exponent) states and converts at the end; the first row whose conversion leaves f64's range is
 // recorded, and a second kernel pair, which ends at once when there is none, rewrites the rows after it from the sticky value.
 // The lag kernel is one stream: a row reads x[i] and x[i - periods] and writes one cell; four lanes build one mask byte.
-#include "engine.hpp"
+#include "cumulative.hpp"
 
 #include <algorithm>
 
@@ -34,20 +34,6 @@ constexpr int CUM_TILE = CUM_WAVES * CUM_WAVE_ROWS;     // 2048 rows: cum_tile_r
 constexpr int CUM_BLOCKS_PER_CU = 4;                    // cum_blocks_per_cu of pandrs_hip.h
 constexpr uint64_t CUM_NONE = ~0ull;                    // the excursion cell: no row left f64's range
 
-struct CumCol {
-    const uint64_t *data;
-    const uint8_t *mask;    // null bits or nullptr
-    int64_t n;
-    int in16;               // data is 16-byte aligned
-};
-
-struct CumOut {
-    uint64_t *data;
-    uint8_t *mask;          // ceil(n / 8) bytes or nullptr
-    uint32_t *n_null;       // += the bits set in the output mask (counted with or without mask)
-    int out16;              // data is 16-byte aligned
-};
-
 struct CumSpans {
     int64_t tiles, base, rem;       // span b holds base + (b < rem) tiles from tile b * base + min(b, rem)
     void *summary;                  // [grid] states
@@ -57,53 +43,13 @@ struct CumSpans {
 // ---- the folds ------------------------------------------------------------------------------------------------------------
 struct ProdState { double m; int64_t e; };              // value = m * 2^e; 0, +-inf and NaN live in m
 
-__device__ __forceinline__ double cum_shfl_up(double v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ uint32_t cum_shfl_up(uint32_t v, int d) { return (uint32_t)__shfl_up((int)v, d, 64); }
 __device__ __forceinline__ ProdState cum_shfl_up(ProdState v, int d) { return ProdState{__shfl_up(v.m, d, 64), (int64_t)__shfl_up((long long)v.e, d, 64)}; }
-__device__ __forceinline__ double cum_shfl(double v, int l) { return __shfl(v, l, 64); }
-__device__ __forceinline__ uint32_t cum_shfl(uint32_t v, int l) { return (uint32_t)__shfl((int)v, l, 64); }
 __device__ __forceinline__ ProdState cum_shfl(ProdState v, int l) { return ProdState{__shfl(v.m, l, 64), (int64_t)__shfl((long long)v.e, l, 64)}; }
-
-__device__ __forceinline__ uint64_t cum_bits(double v) {
-    return v != v ? CANON_NAN : (uint64_t)__double_as_longlong(v);
-}
 
 __device__ __forceinline__ double cum_mant(double v) { return v; }
 __device__ __forceinline__ double cum_mant(uint32_t) { return 0.0; }
 __device__ __forceinline__ double cum_mant(const ProdState &v) { return v.m; }
 
-struct CumSum {
-    using S = double;
-    static constexpr bool IS_PROD = false, IS_COUNT = false;
-    __device__ static S identity() { return -0.0; }     // the exact identity of IEEE addition
-    __device__ static S start() { return 0.0; }         // the reference's fold starts from +0.0
-    __device__ static S combine(S a, S b) { return a + b; }
-    __device__ static S elem(double x, bool null) { return null ? -0.0 : x; }
-    __device__ static uint64_t out(S s) { return cum_bits(s); }
-};
-template <bool MAXOP>
-struct CumExt {
-    using S = double;
-    static constexpr bool IS_PROD = false, IS_COUNT = false;
-    __device__ static S identity() { return MAXOP ? -INFINITY : INFINITY; }
-    __device__ static S start() { return identity(); }
-    // IEEE total order on non-NaN values, -0.0 below +0.0, as pandrs_hip_window's min / max; NaN never gets here
-    __device__ static S combine(S a, S b) {
-        if (MAXOP) return (a > b || (a == b && !signbit(a))) ? a : b;
-        return (a < b || (a == b && signbit(a))) ? a : b;
-    }
-    __device__ static S elem(double x, bool null) { return null || x != x ? identity() : x; }
-    __device__ static uint64_t out(S s) { return (uint64_t)__double_as_longlong(s); }
-};
-struct CumCount {
-    using S = uint32_t;                                 // fewer than 2^32 rows per call
-    static constexpr bool IS_PROD = false, IS_COUNT = true;
-    __device__ static S identity() { return 0; }
-    __device__ static S start() { return 0; }
-    __device__ static S combine(S a, S b) { return a + b; }
-    __device__ static S elem(double x, bool null) { return null || x != x ? 0u : 1u; }
-    __device__ static uint64_t out(S s) { return (uint64_t)s; }
-};
 struct CumProd {
     using S = ProdState;
     static constexpr bool IS_PROD = true, IS_COUNT = false;
@@ -125,10 +71,6 @@ struct CumProd {
 };
 
 // ---- one tile's loads -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double cum_f64(uint64_t v, bool is_i64) {
-    return is_i64 ? (double)(int64_t)v : __longlong_as_double((long long)v);
-}
-
 // the lane's two cells of the load that starts at row r0 (even); rows at or past n read as 0
 __device__ __forceinline__ void cum_load2(const CumCol &c, int64_t r0, bool full, uint64_t &a, uint64_t &b) {
     if (full && c.in16) {
@@ -398,63 +340,6 @@ __global__ __launch_bounds__(CUM_THREADS) void lag_kernel(CumCol c, int64_t tile
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool cum_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-// what pandrs_hip_cumulative and pandrs_hip_lag share: the checks, the staging, the counter; `run` launches the kernels
-template <typename RUN>
-static int32_t cum_call(const char *name, pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t out_mem_space,
-                        void *out_data, uint8_t *out_null_mask, int64_t *out_n_null, RUN run) {
-    if (col->dtype != PANDRS_HIP_I64 && col->dtype != PANDRS_HIP_F64)
-        return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "%s: the column has dtype %d, expected I64 or F64", name, col->dtype);
-    if (n_rows >= (int64_t(1) << 32))
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "%s: %lld rows; one call takes fewer than 2^32", name, (long long)n_rows);
-    if (out_n_null) *out_n_null = 0;
-    if (n_rows == 0) return 0;
-    const size_t n = (size_t)n_rows, nbytes = (n + 7) / 8;
-    if (mem_space == out_mem_space)
-        for (const void *o : {(const void *)out_data, (const void *)out_null_mask})
-            if (cum_overlap(o, o == out_data ? n * 8 : nbytes, col->data, n * 8) || cum_overlap(o, o == out_data ? n * 8 : nbytes, col->null_mask, nbytes))
-                return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "%s: an output overlaps the column; the call cannot run in place", name);
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    timings_begin(c);
-
-    ColView cv{col->data, col->null_mask};
-    void *d_out = out_data;
-    uint8_t *d_omask = out_null_mask;
-    Stager stg{c, mem_space, out_mem_space};
-    const bool stage_mask = out_null_mask && out_mem_space == PANDRS_HIP_MEM_HOST;      // the call's second output: its own slot
-    if (const size_t need = stg.col_size(*col, n_rows) + stg.out_size(out_data, n * 8) + (stage_mask ? Stager::slot(nbytes) : 0)) {
-        PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
-        ST_TRY(stg.reserve(need));
-        cv = stg.col(*col, n_rows);
-        d_out = stg.out(out_data, n * 8);
-        if (stage_mask) d_omask = stg.scratch<uint8_t>(nbytes);
-        if (stg.status) return stg.status;
-    }
-    if ((reinterpret_cast<uintptr_t>(cv.data) | reinterpret_cast<uintptr_t>(d_out)) & 7)
-        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "%s: the column and out_data must be 8-byte aligned", name);
-
-    const CumCol cc{static_cast<const uint64_t *>(cv.data), cv.mask, n_rows, (reinterpret_cast<uintptr_t>(cv.data) & 15) == 0};
-    CumOut co{static_cast<uint64_t *>(d_out), d_omask, nullptr, (reinterpret_cast<uintptr_t>(d_out) & 15) == 0};
-    {
-        PhaseTimer pt(c, PANDRS_HIP_PHASE_AGGREGATE);
-        ST_TRY(run(cc, co));
-        HIP_TRY(hipGetLastError());
-    }
-    ST_TRY(stg.copy_back(n * 8));
-    if (stage_mask) HIP_TRY(hipMemcpyAsync(out_null_mask, d_omask, nbytes, hipMemcpyDeviceToHost, c->stream));
-    uint32_t nulls = 0;
-    HIP_TRY(hipMemcpyAsync(&nulls, co.n_null, 4, hipMemcpyDeviceToHost, c->stream));
-    ST_TRY(timings_end(c));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out_n_null) *out_n_null = (int64_t)nulls;
-    return 0;
-}
-
 template <typename OP, bool RESCAN>
 static void cum_launch(pandrs_hip_ctx *c, int grid, bool is_i64, const CumCol &cc, const CumSpans &sp, const CumOut &co) {
     if (is_i64) {

@@ -98,6 +98,7 @@ class Context:
             _raise(st)
         self.h = h
         self.device = device
+        self.grouping_token = 0     # bumped by every groupby_indices: whose grouping the context retains (see grouped)
 
     def close(self):
         self.comm_destroy()
@@ -261,17 +262,25 @@ class Context:
         self.groupby_compute(keys, n_rows, vals, aggs)
         return self.groupby_fetch()
 
+    def groupby_indices_compute(self, keys, n_rows):
+        """The grouping alone: it stays in the context for groupby_indices' fetch and for any number of grouped() calls.
+        -> (n_groups, memory space of the keys).  Bumps grouping_token: a caller that remembers the value it saw after its
+        own call knows later whether the retained grouping is still its own."""
+        keep = []
+        kc, sp = self._cols(keys, keep)
+        ng = C.c_int64(0)
+        self.grouping_token += 1                        # (a failed call drops the retained grouping too)
+        st = self.lib.pandrs_hip_groupby_indices(self.h, sp, kc, len(keys), int(n_rows), C.byref(ng))
+        if st:
+            _raise(st)
+        return ng.value, sp
+
     def groupby_indices(self, keys, n_rows):
         """group_by's row -> group assignment (grouping.rs:22-115) in CSR form.
         -> (key_cells[n_keys, G] u64, key_null[n_keys, G] u8, offsets[G + 1] i64, rows[n_rows] i64);
         group g = rows[offsets[g]:offsets[g + 1]], ascending."""
-        keep = []
-        kc, sp = self._cols(keys, keep)
-        ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_groupby_indices(self.h, sp, kc, len(keys), int(n_rows), C.byref(ng))
-        if st:
-            _raise(st)
-        g, nk = ng.value, len(keys)
+        g, sp = self.groupby_indices_compute(keys, n_rows)
+        nk = len(keys)
         if sp == L.MEM_DEVICE:
             import torch
             d = "cuda:%d" % self.device
@@ -998,6 +1007,28 @@ class Context:
         nulls = C.c_int64(0)
         st = self.lib.pandrs_hip_lag(self.h, sp, cc, n, op, C.c_int64(periods), L.MEM_DEVICE if out_device else L.MEM_HOST,
                                      _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
+        if st:
+            _raise(st)
+        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+
+    def grouped(self, col, n_rows, op, periods=0, out=None, out_mask=None, out_device=None):
+        """Context.cumulative / Context.lag within the groups this context retains from its last groupby_indices
+        (pandrs_hip_grouped): for every group the ungrouped op over the group's rows in ascending row order, written at those
+        rows.  op is L.GROUPED_CUM_SUM / CUM_MAX / CUM_MIN / CUM_COUNT / ROW_NUMBER / SHIFT / DIFF / PCT_CHANGE; `periods` is
+        read by the last three.  `col` as Context.cumulative; None for ROW_NUMBER, which reads no column.  n_rows must be the
+        grouping's.  Buffers and the result as Context.cumulative; CUM_COUNT and ROW_NUMBER give int64."""
+        keep = []
+        n, op, periods = int(n_rows), int(op), int(periods)
+        if not -(1 << 63) <= periods < (1 << 63):
+            raise ValueError("periods must fit int64, got %d" % periods)
+        if col is None:
+            cc, sp = None, (L.MEM_DEVICE if out_device or _is_torch(out) else L.MEM_HOST)
+        else:
+            cc, sp = self._cols([tuple(col)], keep)
+        out, out_mask, out_device = self._cell_outs(n, sp, op in (L.GROUPED_CUM_COUNT, L.GROUPED_ROW_NUMBER), out, out_mask, out_device)
+        nulls = C.c_int64(0)
+        st = self.lib.pandrs_hip_grouped(self.h, sp, cc, n, op, C.c_int64(periods), L.MEM_DEVICE if out_device else L.MEM_HOST,
+                                         _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
         if st:
             _raise(st)
         return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value

@@ -1677,6 +1677,7 @@ class GroupBy:
         self.group_by_columns = group_by_columns
         self.create_multi_index = create_multi_index
         self._groups = None
+        self._grouping = None       # (context, its grouping_token) after this GroupBy's own groupby_indices
 
     def _group_rows(self, null_string="NULL"):
         """{tuple(key strings) -> ascending row indices (numpy)} from pandrs_hip_groupby_indices."""
@@ -1759,6 +1760,65 @@ class GroupBy:
         return result
 
     par_transform = transform
+
+    # -- folds and lags within the groups (pandrs_hip_grouped): no closure, no sub-frames ---------------------------------
+    def _grouped(self, column_name, op, periods=0):
+        """One pandrs_hip_grouped call -> (values as a host array, null bitmap or None), aligned with the frame's rows.  The
+        grouping is built once and reused while the context still retains it (its grouping_token is this GroupBy's).  Errors
+        before any device call, as the frame-level methods: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column,
+        InvalidValue for negative periods of diff / pct_change; an empty frame gives an empty result."""
+        col = None if column_name is None else self.df._numeric(column_name)
+        periods = int(periods)
+        if op in (L.GROUPED_DIFF, L.GROUPED_PCT_CHANGE) and periods < 0:
+            raise InvalidValue("periods must not be negative, got %d" % periods)
+        n = self.df.row_count()
+        if n == 0:
+            return np.empty(0, np.int64 if op in (L.GROUPED_CUM_COUNT, L.GROUPED_ROW_NUMBER) else np.float64), None
+        ctx = get_context()
+        if self._grouping is None or self._grouping[0] is not ctx or self._grouping[1] != ctx.grouping_token:
+            ctx.groupby_indices_compute([self.df.column(k).view() for k in self.group_by_columns], n)
+            self._grouping = (ctx, ctx.grouping_token)
+        values, mask, _ = ctx.grouped(None if col is None else col.view(), n, op, periods, out_device=False)
+        return np.asarray(values), mask
+
+    def cumsum(self, column):
+        """The running sum of `column` within each group, in row order, -> list of float aligned with the frame's rows
+        (OptimizedDataFrame.cumsum per group; pandrs_hip.h: every group's prefix is folded from its own cells)."""
+        return self._grouped(column, L.GROUPED_CUM_SUM)[0].tolist()
+
+    def cummax(self, column):
+        """OptimizedDataFrame.cummax within each group, -> list of float."""
+        return self._grouped(column, L.GROUPED_CUM_MAX)[0].tolist()
+
+    def cummin(self, column):
+        """OptimizedDataFrame.cummin within each group, -> list of float."""
+        return self._grouped(column, L.GROUPED_CUM_MIN)[0].tolist()
+
+    def cumcount(self, column):
+        """OptimizedDataFrame.cumcount within each group: the group's rows so far that are neither NaN nor null, -> list of int."""
+        return [int(v) for v in self._grouped(column, L.GROUPED_CUM_COUNT)[0]]
+
+    def row_number(self):
+        """The position of every row within its group (0 for the group's first row), null or not, -> list of int."""
+        return [int(v) for v in self._grouped(None, L.GROUPED_ROW_NUMBER)[0]]
+
+    def shift(self, column, periods):
+        """OptimizedDataFrame.shift within each group: a row takes the cell `periods` rows earlier in its group, -> list of
+        float or None (no source row in the group, or a null one)."""
+        values, mask = self._grouped(column, L.GROUPED_SHIFT, periods)
+        out = values.tolist()
+        if mask is not None:
+            for i in np.flatnonzero(np.unpackbits(mask, bitorder="little")[:len(out)]):
+                out[i] = None
+        return out
+
+    def diff(self, column, periods):
+        """OptimizedDataFrame.diff within each group, NaN for a group's first `periods` rows, -> list of float."""
+        return self._grouped(column, L.GROUPED_DIFF, periods)[0].tolist()
+
+    def pct_change(self, column, periods):
+        """OptimizedDataFrame.pct_change within each group, -> list of float."""
+        return self._grouped(column, L.GROUPED_PCT_CHANGE, periods)[0].tolist()
 
     def aggregate(self, aggregations):
         """aggregations: iterable of (column, AggregateOp, alias)  (aggregation.rs:763-871)."""
