@@ -218,6 +218,9 @@ int32_t pandrs_hip_workspace_poisoned_bytes(int64_t *out_bytes);
  *                       global set; 0 = the default, by the list's size (isin_lds_max_values; experiments/predicate_bench.py)
  *   "predicate_path"    tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in its loop; 0 = the
  *                       default, integers compared against the interval the host bisects (the same bits; experiments/predicate_bench.py)
+ *   "bin_path"          tests / experiments: 1 = pandrs_hip_bin always takes the search, 2 = it takes the guess wherever the edges
+ *                       are evenly spaced; 0 = the default, the guess from bin_guess_min_bins evenly spaced bins on (the same
+ *                       codes; experiments/bin_bench.py)
  *   "window_quantile_path"  tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, which serves rolling
  *                       windows of at most 44 rows (a wider or expanding window: PANDRS_HIP_ERR_INVALID_ARGUMENT), 2 = it always
  *                       takes the general (wavelet matrix) path; 0 = the default, by the window (experiments/window_quantile_bench.py)
@@ -944,6 +947,84 @@ int32_t pandrs_hip_predicate(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
 int32_t pandrs_hip_isin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                         int32_t values_mem_space, const pandrs_hip_column *values, int64_t n_values, int32_t negate,
                         int32_t out_mem_space, uint8_t *out_bits, int64_t *out_count);
+
+/* ---- bins of one numeric column: cut, qcut, per-bin counts -----------------------------------------------------------------------
+ * PandasCompatExt::value_range (src/dataframe/pandas_compat/functions.rs:2270-2282), cut (:2339-2368) and qcut (:2370-2420); the
+ * reference's tests at :6840-6846 and :6943-7018.  Both read the column through get_column_numeric_values: every cell in f64, an
+ * I64 cell as (double)v (so 2^53 + 1 falls where 2^53 falls).  With `valid` the cells that are not NaN and m their number:
+ *   cut(bins)   w = (max - min) / bins as f64; e[i] = min + i as f64 * w for i = 0 ..= bins, then e[bins] = max + 0.001.
+ *   qcut(q)     valid in ascending stable order; e[i] = valid[min((m as f64 * i as f64 / q as f64) as usize, m - 1)], i = 0 ..= q;
+ *               when it looks a row up, the last edge is e[q] + 0.001.
+ *   a row       NaN gives "NaN"; any other v the FIRST i in 0 .. bins with v >= e[i] && v < e[i + 1]; a row that matches no bin is
+ *               left out of cut's result (it is shorter than the column: the maximum from about 2^43 upward, where max + 0.001 ==
+ *               max) and is "" in qcut's.  The labels, "(lo, hi]" with {:.2} and "Q{i + 1}", are the mirrors' business.
+ * pandrs_hip_bin_edges returns that edge list (without qcut's + 0.001, which the caller adds), pandrs_hip_bin takes any edge
+ * list and answers per row: the code i, PANDRS_HIP_BIN_NONE (no bin) or PANDRS_HIP_BIN_NAN (a NaN cell), and the rows per code.
+ * With a non-decreasing edge list the first match is i = (the number of edges <= v) - 1 wherever that lies in [0, n_bins):
+ * e[i] <= v < e[i + 1] names i uniquely, and a bin with e[i] == e[i + 1] is empty either way; comparisons are by value (-0.0 ==
+ * +0.0), +-inf edges are allowed, a NaN edge or a decreasing list is refused.  The reference's own lists never decrease except
+ * where rounding leaves cut's e[bins] below e[bins - 1]; passing max(e[bins], e[bins - 1]) there selects the same rows, since no
+ * row lies in [e[bins - 1], e[bins]) either way.  A non-finite w (an infinite min or max, max - min overflowing) makes e[0] NaN
+ * and every bin empty: the caller answers that case from out_valid without a pandrs_hip_bin call.
+ * Exactness: codes and counts are exact (comparisons and integers).  Every edge is bit for bit the reference's: min, max and the
+ * selected elements are the column's own cells (I64: the selected integer as f64, also beyond 2^53), cut's expression is
+ * evaluated on the host, every operation rounded on its own (no fused multiply-add).
+ * Deviations:
+ *  - a cell whose null bit is set behaves as NaN and the cell under the bit is not looked at (the reference fails on a missing
+ *    value, src/dataframe/base.rs:555-561); it is not counted in out_valid.  The position of pandrs_hip_predicate and pandrs_hip_fill.
+ *  - Signed zero: min, max and the selected elements come from the order-preserving code, -0.0 before +0.0 (pandrs_hip_describe),
+ *    so an edge that is zero may differ from the reference's in its sign bit.  No code changes (comparisons are by value); a cut
+ *    label may read "-0.00" for "0.00".
+ *  - no valid cell: pandrs_hip_bin_edges is status OK with *out_valid = 0 and every edge NaN; the reference returns
+ *    Err(InvalidValue) and the mirrors raise it, as for bins == 0 / q == 0.
+ * How, pandrs_hip_bin (bin.hip): one stream over the column, 16-byte loads (two rows per thread and load; a data pointer 8 bytes
+ * off a 16-byte boundary takes 8-byte loads), codes stored as coalesced int32 pairs: 8 bytes read and 4 written per row.  Every
+ * workgroup copies the edges into LDS once ((bin_max_bins + 1) x 8 bytes = 32 KiB + 8 at most; the LDS is sized by n_bins).  Two
+ * searches behind "bin_path": search, a branch-free upper bound of ceil(log2(n_bins + 1)) steps, the same for every lane; guess,
+ * where the host finds e[0 .. n_bins) evenly spaced (n_bins >= 2, w = (e[n_bins - 1] - e[0]) / (n_bins - 1) finite and positive,
+ * every |e[i] - (e[0] + i w)| <= w / 4; the last edge is free): (int)((v - e[0]) / w), clamped and corrected against the real
+ * edges in LDS in at most 2 steps, a lane that is still off takes the search.  What a lane ends with satisfies e[i] <= v <
+ * e[i + 1], so both give the same code for every row, also at an edge and one ulp off it.  "bin_path" 0 takes the guess from
+ * bin_guess_min_bins = 128 evenly spaced bins on (measured: the search wins at 64 bins and loses at 256).  I64 cells are
+ * converted per row.  Counts: a uint32 histogram of n_bins + 2 cells per workgroup in LDS; lanes of a wave that hold the same
+ * code add once (up to 4 codes per wave and row by ballot, given up once a round folds fewer than 4 lanes; the rest by LDS
+ * atomics), flushed with 64-bit atomics to workspace counters when the workgroup ends; out_counts == NULL compiles
+ * the histogram out, out_codes == NULL leaves the histogram alone.  No workgroup waits for another; every row index is 64-bit.
+ * How, pandrs_hip_bin_edges (describe.hip): CUT runs the moments stream of pandrs_hip_describe alone.  QCUT asks that file's
+ * multi-rank radix select for integer ranks instead of percentiles, all weights zero; one selection takes up to 32 distinct
+ * ranks, so k + 1 > 32 runs ceil((k + 1) / 32) selections over the column: correct, not fast.
+ * Geometry (tests read it): bin_max_bins = 4096; bin_tile_rows = 2048 rows per workgroup iteration, bin_blocks_per_cu = 4, grid =
+ * min(bin_blocks_per_cu x compute units, ceil(n_rows / bin_tile_rows)) workgroups striding over the tiles (with counts and more
+ * than about 3400 bins the LDS leaves room for three workgroups per compute unit; the fourth follows).  pandrs_hip_bin_edges has
+ * pandrs_hip_describe's geometry.
+ * Buffers: a host column and a host out_codes are staged; device and resident columns are read in place.  Column data is 8-byte
+ * aligned (16-byte alignment not needed); a null mask at any byte offset, bits past n_rows ignored.  out_codes receives exactly
+ * n_rows int32 (4-byte aligned, no byte past 4 x n_rows written) and may be NULL; out_counts is a host pointer to n_bins + 2
+ * int64, the bins, then NONE, then NAN, summing to n_rows, and may be NULL; not both.  edges, out_edges and out_valid are host
+ * pointers.  pandrs_hip_get_timings: the stream is PANDRS_HIP_PHASE_AGGREGATE and n_partitions says which search ran (1 search,
+ * 2 guess); pandrs_hip_bin_edges: PANDRS_HIP_PHASE_OTHER, n_partitions the number of selections.
+ * Workspace, sized up front, whatever n_rows: pandrs_hip_bin the edges and the counters (12 bytes per bin); pandrs_hip_bin_edges
+ * pandrs_hip_describe's.  Staging: a host column, a host out_codes.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a column
+ * that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a NULL col / edges / out_edges / out_valid, out_codes and out_counts both
+ * NULL, n_bins or k outside 1 .. bin_max_bins, a kind outside the enum, an edge that is NaN or below the one before it, n_rows <
+ * 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  pandrs_hip_bin with n_rows == 0: OK, nothing written to out_codes,
+ * out_counts all zero.
+ * Out of scope: more than 4096 bins; right-closed or labelled pandas-style intervals beyond the reference's strings; binning by a
+ * second column's edges; String columns; a call between 2^31 and 2^32 rows as a tested size (the indexing is 64-bit by
+ * construction); the multi-GPU path; fusing the codes into group_by without materialising them. */
+#define PANDRS_HIP_BIN_MAX_BINS 4096
+#define PANDRS_HIP_BIN_NONE (-1)        /* the row matches no bin */
+#define PANDRS_HIP_BIN_NAN (-2)         /* the cell is NaN or null */
+typedef enum pandrs_hip_bin_kind { PANDRS_HIP_BIN_CUT = 0, PANDRS_HIP_BIN_QCUT = 1 } pandrs_hip_bin_kind;
+
+int32_t pandrs_hip_bin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *edges,
+                       int32_t n_bins, int32_t out_mem_space, int32_t *out_codes, int64_t *out_counts);
+
+/* kind = pandrs_hip_bin_kind, k = bins (CUT) or q (QCUT); out_edges receives k + 1 doubles, *out_valid the cells that are
+ * neither null nor NaN. */
+int32_t pandrs_hip_bin_edges(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind,
+                             int32_t k, double *out_edges, int64_t *out_valid);
 
 /* ---- running folds and lagged differences of one numeric column: cumsum, cumprod, cummax, cummin, cumcount, shift, diff ------
  * PandasCompatExt::cumsum / cumprod / cummax / cummin (src/dataframe/pandas_compat/functions.rs:280-327), shift (:328-342),

@@ -13,6 +13,7 @@
 //                             describe / describe_all: src/optimized/split_dataframe/stats.rs:50-171
 //                             rank: src/dataframe/pandas_compat/functions.rs:193-236
 //                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
+//                             value_range / cut / qcut: functions.rs:2270-2282, :2339-2420
 //                             gt / ge / lt / le / eq_value / ne_value: pandas_compat/helpers/comparison_ops.rs:7-46;
 //                             between / is_between / isna / notna / is_finite / is_infinite / isin / isin_numeric /
 //                             query_* / dropna / count_na / has_nulls / count_value: functions.rs:141-158, :253-257,
@@ -32,6 +33,7 @@
 #include <charconv>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -396,6 +398,53 @@ public:
     // (min_by), NaN and null cells skipped; nullopt when the column holds no number.  One pandrs_hip_arg_extreme pass for both.
     std::optional<size_t> idxmax(const std::string &column_name) const { return arg_extreme(column_name, 1); }
     std::optional<size_t> idxmin(const std::string &column_name) const { return arg_extreme(column_name, 0); }
+    // value_range / cut / qcut (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:2270-2282, :2339-2420).  value_range:
+    // (min, max) over the cells that are not NaN, from the whole-column reduction.  cut: `bins` equal-width bins over that range,
+    // the last edge max + 0.001; "(lo, hi]" with two decimals for the first bin with lo <= v < hi, "NaN" for a NaN or null cell,
+    // and NO entry for a row that matches no bin (the maximum once max + 0.001 == max): the vector is then shorter than the
+    // column, as the reference's is.  qcut: edges at valid[min(m * i / q, m - 1)], "Q{i + 1}", "NaN", "" for a row in no bin.
+    // One pandrs_hip_bin_edges call (the reference's edge list, bit for bit) and one pandrs_hip_bin call each.  InvalidValue for
+    // bins == 0 / q == 0, more than PANDRS_HIP_BIN_MAX_BINS, or no valid cell; ColumnNotFound / Type before any device call.
+    std::pair<double, double> value_range(const std::string &column_name) const {
+        numeric(column_name);
+        if (!row_count_) throw Error(Error::InvalidValue, "No valid values in column");
+        const pandrs_hip_column_stats st = stats(column_name);
+        if (st.min > st.max) throw Error(Error::InvalidValue, "No valid values in column");
+        return {st.min, st.max};
+    }
+    std::vector<std::string> cut(const std::string &column_name, size_t bins) const {
+        numeric(column_name);
+        if (bins == 0) throw Error(Error::InvalidValue, "Number of bins must be > 0");
+        std::vector<double> edges;
+        std::vector<int32_t> codes;
+        const size_t n_nan = bin(column_name, PANDRS_HIP_BIN_CUT, bins, "No valid values in column", edges, codes);
+        if (codes.empty() && row_count_) return std::vector<std::string>(n_nan, "NaN");     // w is not finite: every bin is empty
+        std::vector<std::string> labels(bins), out;
+        out.reserve(row_count_);
+        for (int32_t code : codes) {
+            if (code == PANDRS_HIP_BIN_NONE) continue;
+            if (code == PANDRS_HIP_BIN_NAN) { out.emplace_back("NaN"); continue; }
+            if (labels[(size_t)code].empty()) {
+                char buf[700];                                                              // two %.2f of any finite double
+                std::snprintf(buf, sizeof buf, "(%.2f, %.2f]", edges[(size_t)code], edges[(size_t)code + 1]);
+                labels[(size_t)code] = buf;
+            }
+            out.push_back(labels[(size_t)code]);
+        }
+        return out;
+    }
+    std::vector<std::string> qcut(const std::string &column_name, size_t q) const {
+        numeric(column_name);
+        if (q == 0) throw Error(Error::InvalidValue, "Number of quantiles must be > 0");
+        std::vector<double> edges;
+        std::vector<int32_t> codes;
+        bin(column_name, PANDRS_HIP_BIN_QCUT, q, "No valid values", edges, codes);
+        std::vector<std::string> out(row_count_);
+        for (size_t r = 0; r < row_count_; r++)
+            if (codes[r] == PANDRS_HIP_BIN_NAN) out[r] = "NaN";
+            else if (codes[r] >= 0) out[r] = "Q" + std::to_string(codes[r] + 1);
+        return out;
+    }
     // cumsum / cumprod / cummax / cummin / cumcount / shift / diff / pct_change (PandasCompatExt,
     // src/dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094): the reference's vectors from one
     // pandrs_hip_cumulative or pandrs_hip_lag call.  Errors before any device call: ColumnNotFound, Type (a String or Boolean
@@ -1065,6 +1114,25 @@ private:
         return {std::move(out), n};
     }
 
+    // cut / qcut: the edge list (kind = pandrs_hip_bin_kind), then every row's code against it -> the NaN rows.  `codes` stays
+    // empty where cut's w is not finite (e[0] is NaN then and every bin is empty, pandrs_hip.h).
+    size_t bin(const std::string &name, int32_t kind, size_t k, const char *no_valid, std::vector<double> &edges, std::vector<int32_t> &codes) const {
+        if (k > PANDRS_HIP_BIN_MAX_BINS) throw Error(Error::InvalidValue, "at most " + std::to_string(PANDRS_HIP_BIN_MAX_BINS) + " bins");
+        if (!row_count_) throw Error(Error::InvalidValue, no_valid);
+        const pandrs_hip_column v = view_of(name);
+        edges.assign(k + 1, 0.0);
+        int64_t valid = 0;
+        detail::check(pandrs_hip_bin_edges(detail::context(), mem_space(), &v, (int64_t)row_count_, kind, (int32_t)k, edges.data(), &valid));
+        if (valid == 0) throw Error(Error::InvalidValue, no_valid);
+        if (edges[0] != edges[0]) return row_count_ - (size_t)valid;
+        std::vector<double> look = edges;
+        if (kind == PANDRS_HIP_BIN_QCUT) look[k] = edges[k] + 0.001;                        // functions.rs:2406-2407
+        else if (look[k] < look[k - 1]) look[k] = look[k - 1];                              // (for the search only: no row lies between them)
+        codes.assign(row_count_, 0);
+        detail::check(pandrs_hip_bin(detail::context(), mem_space(), &v, (int64_t)row_count_, look.data(), (int32_t)k, PANDRS_HIP_MEM_HOST,
+                                     codes.data(), nullptr));
+        return row_count_ - (size_t)valid;
+    }
     pandrs_hip_column_stats stats(const std::string &name) const {
         const Column &c = column(name);
         if (c.index() > 1) throw Error(Error::Type, "Column '" + name + "' is not a numeric type");      // aggregate.rs:57

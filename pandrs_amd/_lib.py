@@ -35,6 +35,8 @@ EVAL_COL, EVAL_CONST, EVAL_ADD, EVAL_SUB, EVAL_MUL, EVAL_DIV, EVAL_REM, EVAL_MAX
     EVAL_TRUNC, EVAL_ROUND, EVAL_FRACT, EVAL_SQRT, EVAL_SIGN, EVAL_GT, EVAL_GE, EVAL_LT, EVAL_LE, EVAL_EQ, EVAL_NE, EVAL_ISNAN, EVAL_ISINF, \
     EVAL_ISFINITE, EVAL_AND, EVAL_OR, EVAL_NOT, EVAL_SELECT = range(31)
 EVAL_MAX_OPS, EVAL_MAX_COLS, EVAL_MAX_DEPTH = 64, 8, 8
+BIN_CUT, BIN_QCUT = range(2)
+BIN_NONE, BIN_NAN, BIN_MAX_BINS = -1, -2, 4096
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -178,6 +180,10 @@ SYMBOLS = {
                                    C.POINTER(C.c_int64)]),
     "pandrs_hip_grouped": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P,
                                        C.POINTER(C.c_int64)]),
+    "pandrs_hip_bin": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_int32, _P,
+                                   C.POINTER(C.c_int64)]),
+    "pandrs_hip_bin_edges": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int64)]),
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -262,6 +262,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "topk_path")) c->opt.topk_path = value;
     else if (!std::strcmp(name, "isin_path")) c->opt.isin_path = value;
     else if (!std::strcmp(name, "predicate_path")) c->opt.predicate_path = value;
+    else if (!std::strcmp(name, "bin_path")) c->opt.bin_path = value;
     else if (!std::strcmp(name, "window_quantile_path")) c->opt.window_quantile_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
@@ -584,6 +585,20 @@ int32_t pandrs_hip_grouped(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::grouped_entry(ctx, mem_space, col, n_rows, op, periods, out_mem_space, out_data, out_null_mask, out_n_null);
 } catch (...) { return pandrs::on_exception("pandrs_hip_grouped"); }
+
+int32_t pandrs_hip_bin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *edges,
+                       int32_t n_bins, int32_t out_mem_space, int32_t *out_codes, int64_t *out_counts) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "bin: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::bin_entry(ctx, mem_space, col, n_rows, edges, n_bins, out_mem_space, out_codes, out_counts);
+} catch (...) { return pandrs::on_exception("pandrs_hip_bin"); }
+
+int32_t pandrs_hip_bin_edges(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind,
+                             int32_t k, double *out_edges, int64_t *out_valid) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "bin_edges: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::bin_edges_entry(ctx, mem_space, col, n_rows, kind, k, out_edges, out_valid);
+} catch (...) { return pandrs::on_exception("pandrs_hip_bin_edges"); }
 
 int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
                         const int32_t *ops, const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,

@@ -257,6 +257,7 @@ struct Options {
     int64_t topk_path = 0;           // tests / experiments: 1 = pandrs_hip_topk always sorts the column, -1 = it always selects (0 = by the cut-over)
     int64_t isin_path = 0;           // tests / experiments: 1 = pandrs_hip_isin takes the LDS set wherever the list fits, 2 = always the global set (0 = by the list's size)
     int64_t predicate_path = 0;      // tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in the loop instead of comparing integers against the bisected interval
+    int64_t bin_path = 0;            // tests / experiments: 1 = pandrs_hip_bin always searches, 2 = it guesses wherever the edges are evenly spaced (0 = the guess from bin_guess_min_bins bins on)
     int64_t window_quantile_path = 0;   // tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, 2 = the general (wavelet matrix) path (0 = by the window)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
@@ -409,6 +410,13 @@ int32_t window_quantile_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs
 // describe.hip: out_stats != nullptr = describe (25 / 50 / 75 and the moments), else the caller's percentiles
 int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *percentiles,
                        int32_t n_percentiles, double *out_q, int64_t *out_count, pandrs_hip_describe_stats *out_stats);
+// describe.hip: the edge list of cut (kind PANDRS_HIP_BIN_CUT: min + i * w from the moments pass) or qcut (PANDRS_HIP_BIN_QCUT:
+// order statistics at integer ranks from the radix select), k + 1 doubles, and the number of cells that are neither null nor NaN
+int32_t bin_edges_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind, int32_t k,
+                        double *out_edges, int64_t *out_valid);
+// bin.hip: per row the i with edges[i] <= v < edges[i + 1] (or PANDRS_HIP_BIN_NONE / PANDRS_HIP_BIN_NAN), and the rows per code
+int32_t bin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *edges, int32_t n_bins,
+                  int32_t out_mem_space, int32_t *out_codes, int64_t *out_counts);
 // rank.hip: the ascending 1-based rank of every row (method = pandrs_hip_rank_method), NaN for NaN and null cells
 int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method,
                    int32_t out_mem_space, double *out);

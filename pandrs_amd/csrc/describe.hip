@@ -19,6 +19,10 @@
 //    The host enqueues all eight passes; a pass beyond the width returns at once.
 // 4. Finish (one thread): decodes the selected codes (I64: the selected integer `as f64`), interpolates with the reference's
 //    expression, FMA contraction off, and writes the results where the entry's one copy picks them up.
+// 5. Ranks by number (pandrs_hip_bin_edges): a request may name integer ranks among the cells that are neither null nor NaN
+//    instead of percentiles: QCUT(q) asks for min((uint64)((double)m * (double)i / (double)q), m - 1), i = i0 .. i0 + n, m the
+//    count of those cells, known in step 2.  Up to DS_MAX_SLOTS ranks per selection, every weight zero: ds_finish_ranks_kernel
+//    returns the decoded elements with min, max and m.  CUT needs min and max only: steps 1 and 2, no selection.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -49,6 +53,7 @@ struct DsCol {
 struct DsReq {
     double p[DS_MAX_P];
     int32_t n_p;
+    int32_t rank_q, rank_i0, rank_n;      // ranks by number: QCUT(rank_q)'s ranks i0 .. i0 + rank_n (rank_n <= DS_MAX_SLOTS; n_p is 0 then)
 };
 
 struct DsPart {               // one workgroup's moments
@@ -66,6 +71,7 @@ struct DsState {
     uint64_t s_rank[DS_MAX_SLOTS];        // the slot's rank among its group's rows
     int32_t s_group[DS_MAX_SLOTS];        // -1: the rank lies in the NaN block
     uint64_t g_prefix[DS_MAX_SLOTS];      // the digits of d chosen so far
+    int32_t r_slot[DS_MAX_SLOTS];         // ranks by number: the slot of each requested rank
 };
 
 __device__ __forceinline__ bool ds_is_nan(uint64_t b, int i64) { return !i64 && (b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
@@ -205,6 +211,12 @@ __global__ __launch_bounds__(DS_THREADS) void ds_ranks_kernel(const DsPart *part
         tgt[n_t++] = lo[j];
         tgt[n_t++] = hi[j];
     }
+    uint64_t rk[DS_MAX_SLOTS];
+    const int n_r = n_num ? min(req.rank_n, DS_MAX_SLOTS - n_t) : 0;
+    for (int j = 0; j < n_r; j++) {                      // functions.rs:2394-2395; never decreasing in i
+        const uint64_t idx = (uint64_t)((double)n_num * (double)(req.rank_i0 + j) / (double)req.rank_q);
+        tgt[n_t++] = rk[j] = idx < n_num - 1 ? idx : n_num - 1;
+    }
     for (int a = 1; a < n_t; a++) {                      // ascending, then distinct
         const uint64_t x = tgt[a];
         int b = a - 1;
@@ -225,6 +237,9 @@ __global__ __launch_bounds__(DS_THREADS) void ds_ranks_kernel(const DsPart *part
             if (st->s_rank[s] == lo[j]) st->p_lo[j] = s;
             if (st->s_rank[s] == hi[j]) st->p_hi[j] = s;
         }
+    for (int j = 0; j < n_r; j++)
+        for (int s = 0; s < n_s; s++)
+            if (st->s_rank[s] == rk[j]) st->r_slot[j] = s;
     const uint64_t span = n_num ? p.mx - p.mn : 0;
     const int width = span ? 64 - __clzll((long long)span) : 0;
     st->n_slots = n_s;
@@ -390,7 +405,61 @@ __global__ void ds_finish_kernel(const DsState *st, DsReq req, int i64, int desc
     ds->max = st->nan ? (double)NAN : ds_decode(st->mx, i64);         // sorted[count - 1]
 }
 
+// ranks by number.  out: [0] m, the cells that are neither null nor NaN (int64), [1] their min, [2] their max (NaN without
+// one), [3 .. 3 + rank_n) the elements at the requested ranks
+constexpr int DS_RANK_OUT = 3 + DS_MAX_SLOTS;
+__global__ void ds_finish_ranks_kernel(const DsState *st, DsReq req, int i64, double *out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint64_t n_num = st->nn - st->nan;
+    reinterpret_cast<int64_t *>(out)[0] = (int64_t)n_num;
+    out[1] = n_num ? ds_decode(st->mn, i64) : (double)NAN;
+    out[2] = n_num ? ds_decode(st->mx, i64) : (double)NAN;
+    for (int j = 0; j < req.rank_n && j < DS_MAX_SLOTS; j++)
+        out[3 + j] = n_num ? ds_decode(st->mn + st->g_prefix[st->s_group[st->r_slot[j]]], i64) : (double)NAN;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
+// the workspace does not grow with n_rows: per-workgroup partials, the digit counts, the slots, the results
+struct DsWork {
+    int grid;
+    DsPart *part;
+    double *ssq_part;
+    uint32_t *hist;
+    DsState *st;
+    double *d_out;
+};
+constexpr size_t DS_HIST_N = (size_t)DS_MAX_SLOTS * DS_BINS;
+constexpr size_t DS_DESCRIBE_OUT = 1 + DS_MAX_P + sizeof(pandrs_hip_describe_stats) / 8;
+constexpr size_t DS_OUT_DOUBLES = DS_DESCRIBE_OUT > (size_t)DS_RANK_OUT ? DS_DESCRIBE_OUT : (size_t)DS_RANK_OUT;
+
+static int32_t ds_work(pandrs_hip_ctx *c, int64_t n, const char *who, DsWork &w) {
+    const int64_t tiles = (n + DS_TILE - 1) / DS_TILE;
+    w.grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * DS_BLOCKS_PER_CU, tiles));
+    ST_TRY(c->temp.ensure(Arena::padded((size_t)w.grid * sizeof(DsPart)) + Arena::padded((size_t)w.grid * 8) + Arena::padded(DS_HIST_N * 4) +
+                          Arena::padded(sizeof(DsState)) + Arena::padded(DS_OUT_DOUBLES * 8) + 4096, c->stream));
+    w.part = c->temp.take<DsPart>((size_t)w.grid);
+    w.ssq_part = c->temp.take<double>((size_t)w.grid);
+    w.hist = c->temp.take<uint32_t>(DS_HIST_N);
+    w.st = c->temp.take<DsState>(1);
+    w.d_out = c->temp.take<double>(DS_OUT_DOUBLES);
+    if (!w.part || !w.ssq_part || !w.hist || !w.st || !w.d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (%s)", who);
+    return 0;
+}
+
+// moments and ranks, then (select) the eight digit passes; the caller enqueues its finish kernel behind them
+static int32_t ds_enqueue(pandrs_hip_ctx *c, const DsCol &dc, const DsReq &req, const DsWork &w, bool select) {
+    HIP_TRY(hipMemsetAsync(w.hist, 0, DS_HIST_N * 4, c->stream));
+    hipLaunchKernelGGL(ds_moments_kernel, dim3(w.grid), dim3(DS_THREADS), 0, c->stream, dc, w.part);
+    hipLaunchKernelGGL(ds_ranks_kernel, dim3(1), dim3(DS_THREADS), 0, c->stream, (const DsPart *)w.part, w.grid, req, w.st);
+    HIP_TRY(hipGetLastError());
+    for (int pass = 0; select && pass < DS_MAX_PASSES; pass++) {
+        hipLaunchKernelGGL(ds_select_kernel, dim3(w.grid), dim3(DS_THREADS), 0, c->stream, dc, (const DsState *)w.st, pass, w.hist, w.ssq_part,
+                           reinterpret_cast<unsigned long long *>(&w.st->vary));
+        hipLaunchKernelGGL(ds_pick_kernel, dim3(1), dim3(DS_THREADS), 0, c->stream, w.st, pass, w.hist, (const double *)w.ssq_part, w.grid);
+    }
+    return 0;
+}
+
 int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *percentiles,
                        int32_t n_percentiles, double *out_q, int64_t *out_count, pandrs_hip_describe_stats *out_stats) {
     const char *who = out_stats ? "describe" : "quantiles";
@@ -419,7 +488,7 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
     HIP_TRY(hipSetDevice(c->device));
     timings_begin(c);
     const int64_t n = n_rows;
-    const size_t out_doubles = 1 + DS_MAX_P + sizeof(pandrs_hip_describe_stats) / 8;
+    const size_t out_doubles = DS_DESCRIBE_OUT;
     double *h_out = static_cast<double *>(c->pinned);
     if (n == 0) {                                           // no cell at all: count 0, NaN results
         reinterpret_cast<int64_t *>(h_out)[0] = 0;
@@ -427,18 +496,8 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
         reinterpret_cast<int64_t *>(h_out + 1 + DS_MAX_P)[0] = 0;
         ST_TRY(timings_end(c));
     } else {
-        // ---- the workspace does not grow with n_rows: per-workgroup partials, the digit counts, the slots, the results ----
-        const int64_t tiles = (n + DS_TILE - 1) / DS_TILE;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * DS_BLOCKS_PER_CU, tiles));
-        const size_t hist_n = (size_t)DS_MAX_SLOTS * DS_BINS;
-        ST_TRY(c->temp.ensure(Arena::padded((size_t)grid * sizeof(DsPart)) + Arena::padded((size_t)grid * 8) + Arena::padded(hist_n * 4) +
-                              Arena::padded(sizeof(DsState)) + Arena::padded(out_doubles * 8) + 4096, c->stream));
-        DsPart *part = c->temp.take<DsPart>((size_t)grid);
-        double *ssq_part = c->temp.take<double>((size_t)grid);
-        uint32_t *hist = c->temp.take<uint32_t>(hist_n);
-        DsState *st = c->temp.take<DsState>(1);
-        double *d_out = c->temp.take<double>(out_doubles);
-        if (!part || !ssq_part || !hist || !st || !d_out) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (%s)", who);
+        DsWork w{};
+        ST_TRY(ds_work(c, n, who, w));
         ColView cv{col->data, col->null_mask};
         Stager stg{c, mem_space};
         if (const size_t need = stg.col_size(*col, n)) {
@@ -451,19 +510,11 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
         const DsCol dc{static_cast<const uint64_t *>(cv.data), cv.mask, n, col->dtype == PANDRS_HIP_I64 ? 1 : 0};
         {
             PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
-            HIP_TRY(hipMemsetAsync(hist, 0, hist_n * 4, c->stream));
-            hipLaunchKernelGGL(ds_moments_kernel, dim3(grid), dim3(DS_THREADS), 0, c->stream, dc, part);
-            hipLaunchKernelGGL(ds_ranks_kernel, dim3(1), dim3(DS_THREADS), 0, c->stream, (const DsPart *)part, grid, req, st);
-            HIP_TRY(hipGetLastError());
-            for (int pass = 0; pass < DS_MAX_PASSES; pass++) {
-                hipLaunchKernelGGL(ds_select_kernel, dim3(grid), dim3(DS_THREADS), 0, c->stream, dc, (const DsState *)st, pass, hist, ssq_part,
-                                   reinterpret_cast<unsigned long long *>(&st->vary));
-                hipLaunchKernelGGL(ds_pick_kernel, dim3(1), dim3(DS_THREADS), 0, c->stream, st, pass, hist, (const double *)ssq_part, grid);
-            }
-            hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(64), 0, c->stream, (const DsState *)st, req, dc.i64, out_stats ? 1 : 0, d_out);
+            ST_TRY(ds_enqueue(c, dc, req, w, true));
+            hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(64), 0, c->stream, (const DsState *)w.st, req, dc.i64, out_stats ? 1 : 0, w.d_out);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(h_out, d_out, out_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_out, w.d_out, out_doubles * 8, hipMemcpyDeviceToHost, c->stream));
         c->timings.algorithmic_bytes = (int64_t)n * 8 + (col->null_mask ? (n + 7) / 8 : 0);      // the column (+ mask), once
         ST_TRY(timings_end(c));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -473,6 +524,81 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
         *out_count = reinterpret_cast<const int64_t *>(h_out)[0];
         for (int j = 0; j < req.n_p; j++) out_q[j] = h_out[1 + j];
     }
+    return 0;
+}
+
+// The reference's edge list (functions.rs:2349-2351, :2392-2397).  CUT: min and max from the moments pass, the edges built here.
+// QCUT(k): the k + 1 elements at the ranks above, DS_MAX_SLOTS per selection, so k + 1 > DS_MAX_SLOTS runs
+// ceil((k + 1) / DS_MAX_SLOTS) selections over the column, each with its own moments pass: correct, not fast.
+int32_t bin_edges_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind, int32_t k,
+                        double *out_edges, int64_t *out_valid) {
+    if (!c || !col || n_rows < 0 || (n_rows > 0 && !col->data) || !out_edges || !out_valid)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bin_edges: bad arguments");
+    ST_TRY(check_mem_space("bin_edges", mem_space));
+    if (kind != PANDRS_HIP_BIN_CUT && kind != PANDRS_HIP_BIN_QCUT)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bin_edges: kind %d is not a pandrs_hip_bin_kind", kind);
+    if (col->dtype != PANDRS_HIP_I64 && col->dtype != PANDRS_HIP_F64)
+        return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "bin_edges: the column has dtype %d, expected I64 or F64", col->dtype);
+    if (k < 1 || k > PANDRS_HIP_BIN_MAX_BINS)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bin_edges: k = %d; one call takes 1 to %d", k, PANDRS_HIP_BIN_MAX_BINS);
+    if (n_rows >= (int64_t(1) << 32))
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bin_edges: %lld rows; one call takes fewer than 2^32", (long long)n_rows);
+    *out_valid = 0;
+    for (int32_t i = 0; i <= k; i++) out_edges[i] = NAN;
+    if (n_rows == 0) return 0;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    timings_begin(c);
+    const int64_t n = n_rows;
+    DsWork w{};
+    ST_TRY(ds_work(c, n, "bin_edges", w));
+    ColView cv{col->data, col->null_mask};
+    Stager stg{c, mem_space};
+    if (const size_t need = stg.col_size(*col, n)) {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
+        ST_TRY(stg.reserve(need));
+        cv = stg.col(*col, n);
+        if (stg.status) return stg.status;
+    }
+    if (reinterpret_cast<uintptr_t>(cv.data) & 7) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "bin_edges: the column must be 8-byte aligned");
+    const DsCol dc{static_cast<const uint64_t *>(cv.data), cv.mask, n, col->dtype == PANDRS_HIP_I64 ? 1 : 0};
+    // one block of DS_RANK_OUT doubles per selection in the pinned block; the copies are ordered by the stream
+    const int n_sel = kind == PANDRS_HIP_BIN_QCUT ? (k + 1 + DS_MAX_SLOTS - 1) / DS_MAX_SLOTS : 1;
+    static_assert(((size_t)PANDRS_HIP_BIN_MAX_BINS + 1 + DS_MAX_SLOTS - 1) / DS_MAX_SLOTS * DS_RANK_OUT * 8 <= (1 << 16),
+                  "the selections of a call fit the context's pinned block");
+    double *h_out = static_cast<double *>(c->pinned);
+    {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
+        for (int s = 0; s < n_sel; s++) {
+            DsReq req{};
+            if (kind == PANDRS_HIP_BIN_QCUT) {
+                req.rank_q = k;
+                req.rank_i0 = s * DS_MAX_SLOTS;
+                req.rank_n = std::min(DS_MAX_SLOTS, k + 1 - req.rank_i0);
+            }
+            ST_TRY(ds_enqueue(c, dc, req, w, kind == PANDRS_HIP_BIN_QCUT));
+            hipLaunchKernelGGL(ds_finish_ranks_kernel, dim3(1), dim3(64), 0, c->stream, (const DsState *)w.st, req, dc.i64, w.d_out);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_out + (size_t)s * DS_RANK_OUT, w.d_out, (size_t)DS_RANK_OUT * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    c->timings.n_partitions = n_sel;
+    c->timings.algorithmic_bytes = (int64_t)n * 8 + (col->null_mask ? (n + 7) / 8 : 0);          // the column (+ mask), once
+    ST_TRY(timings_end(c));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t m = reinterpret_cast<const int64_t *>(h_out)[0];
+    *out_valid = m;
+    if (m == 0) return 0;                                // (the edges stay NaN)
+    if (kind == PANDRS_HIP_BIN_QCUT) {
+        for (int32_t i = 0; i <= k; i++) out_edges[i] = h_out[(size_t)(i / DS_MAX_SLOTS) * DS_RANK_OUT + 3 + i % DS_MAX_SLOTS];
+        return 0;
+    }
+    // functions.rs:2349-2351, every operation rounded on its own: this file compiles with fp contract(off), so i * w + min is a
+    // multiplication and an addition, never a fused multiply-add
+    const double mn = h_out[1], mx = h_out[2];
+    const double width = (mx - mn) / (double)k;
+    for (int32_t i = 0; i <= k; i++) out_edges[i] = mn + (double)i * width;
+    out_edges[k] = mx + 0.001;
     return 0;
 }
 

@@ -1133,6 +1133,75 @@ class Context:
             _raise(st)
         return (None if out is None else out[:(n + 7) // 8]), cnt.value
 
+    # -- bins (the edge list from the radix select, one stream for the codes and the counts) ------------------------------
+    def bin_edges(self, col, n_rows, kind, k):
+        """The reference's edge list of cut (kind L.BIN_CUT, k = bins) or qcut (L.BIN_QCUT, k = q) for one I64 / F64 column
+        on the device (pandrs_hip_bin_edges; PandasCompatExt::cut / qcut, src/dataframe/pandas_compat/functions.rs:2349-2351,
+        :2392-2397), bit for bit.  `col` is a (data, mask, dtype) triple on the host or the device, or a ResidentColumn.
+        -> (k + 1 float64 edges as a numpy array, the number of cells that are neither null nor NaN); no such cell: every
+        edge is NaN.  qcut adds 0.001 to the last edge when it looks rows up: that is the caller's step."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        k = int(k)
+        out = np.empty(max(k, 0) + 1, np.float64)
+        valid = C.c_int64(0)
+        st = self.lib.pandrs_hip_bin_edges(self.h, sp, cc, int(n_rows), int(kind), k, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                           C.byref(valid))
+        if st:
+            _raise(st)
+        return out, valid.value
+
+    def _codes_out(self, n, sp, out, out_device, want_codes):
+        """The out_codes buffer of bin, as _mask_out: -> (buffer or None, lives on the device)."""
+        if not want_codes:
+            if out is not None:
+                raise ValueError("want_codes=False takes no out")
+            return None, False
+        if out is not None:
+            out_device = _is_torch(out)
+            if out_device:
+                import torch
+                ok = out.dtype == torch.int32 and out.is_contiguous() and out.is_cuda and out.numel() >= n
+            else:
+                ok = isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.size >= n
+            if not ok:
+                raise ValueError("out must be a contiguous int32 numpy array or CUDA tensor of at least n_rows elements")
+            if out_device:
+                self._wait_for_producer()
+            return out, out_device
+        if out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        if out_device:
+            import torch
+            return torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device), True
+        return np.empty(n, np.int32), False
+
+    def bin(self, col, n_rows, edges, out_device=None, want_counts=True, out=None, want_codes=True):
+        """The bin of every row of one I64 / F64 column on the device (pandrs_hip_bin): code i where edges[i] <= v <
+        edges[i + 1] - the reference's first match, functions.rs:2358-2363 / :2404-2415 - L.BIN_NONE (-1) where no bin
+        matches, L.BIN_NAN (-2) for a NaN or null cell.  `edges`: len(edges) - 1 = 1 ... L.BIN_MAX_BINS bins, never
+        decreasing, no NaN, +-inf allowed.  `col` as in bin_edges.  `out`: an int32 numpy array or torch CUDA tensor of at
+        least n_rows elements to write into.  -> (codes, counts): the int32 codes (`out` when given; else a torch tensor on
+        this context's device for device / resident columns or out_device=True, else a numpy array; None with
+        want_codes=False) and the int64 rows per code as a numpy array of n_bins + 2, the bins, then NONE, then NAN (None
+        with want_counts=False)."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        n = int(n_rows)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        n_bins = e.shape[0] - 1
+        if not want_codes and not want_counts:
+            raise ValueError("bin: neither codes nor counts asked for")
+        out, out_device = self._codes_out(n, sp, out, out_device, want_codes)
+        # (no rows: no codes pointer is passed, so the counts stand for "something asked for")
+        counts = np.zeros(max(n_bins, 0) + 2, np.int64) if want_counts or n == 0 else None
+        st = self.lib.pandrs_hip_bin(self.h, sp, cc, n, e.ctypes.data_as(C.POINTER(C.c_double)), n_bins,
+                                     L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if n and out is not None else None,
+                                     None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_int64)))
+        if st:
+            _raise(st)
+        return (None if out is None else out[:n]), (counts if want_counts else None)
+
     # -- derived columns (one postfix program over up to eight columns, one stream) ---------------------------------------
     @staticmethod
     def eval_check(dtypes, program):

@@ -770,6 +770,94 @@ class OptimizedDataFrame:
         (Iterator::min_by), NaN and null cells skipped; None when the column holds no number.  One device pass."""
         return self._idx_extreme(column, 0)
 
+    # -- value_range / cut / qcut (dataframe/pandas_compat/functions.rs:2270-2282, :2339-2420) ----------------------
+    def value_range(self, column):
+        """PandasCompatExt::value_range (functions.rs:2270-2282): (min, max) over the cells that are not NaN, from the
+        whole-column reduction.  InvalidValue when there is no such cell.  Errors before any device call: ColumnNotFound,
+        ColumnTypeMismatch for a String or Boolean column."""
+        c = self._numeric(column)
+        if c.len() == 0:
+            raise InvalidValue("No valid values in column")
+        st = get_context().column_stats(c.view(), c.len())
+        lo, hi = float(st["min"]), float(st["max"])
+        if lo > hi:                                                      # the fold identities: no cell that is not NaN
+            raise InvalidValue("No valid values in column")
+        return lo, hi
+
+    def bin_codes(self, column, edges):
+        """The bin of every row against a caller's edge list, for callers that go on with the codes (group_by the bucket):
+        one pandrs_hip_bin call -> (codes, counts).  codes: int32 numpy array, i where edges[i] <= v < edges[i + 1] (the
+        reference's first match), L.BIN_NONE (-1) for a row in no bin, L.BIN_NAN (-2) for a NaN or null cell; counts: int64
+        numpy array of len(edges) + 1, the rows per bin, then NONE, then NAN.  `edges` never decrease and hold no NaN
+        (InvalidValue otherwise, as for fewer than 2 or more than L.BIN_MAX_BINS + 1 edges)."""
+        c = self._numeric(column)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if not 2 <= e.shape[0] <= L.BIN_MAX_BINS + 1:
+            raise InvalidValue("bin_codes takes 2 to %d edges, got %d" % (L.BIN_MAX_BINS + 1, e.shape[0]))
+        if np.isnan(e).any() or (np.diff(e) < 0).any():
+            raise InvalidValue("the edges must not decrease and none may be NaN")
+        if c.len() == 0:
+            return np.empty(0, np.int32), np.zeros(e.shape[0] + 1, np.int64)
+        codes, counts = get_context().bin(c.view(), c.len(), e, out_device=False)
+        return np.asarray(codes), counts
+
+    def _bin_labels(self, c, kind, k, what):
+        """-> (codes or None, edges, NaN rows): the edge list from one pandrs_hip_bin_edges call and the codes from one
+        pandrs_hip_bin call against it.  codes is None where the reference's w is not finite: e[0] is NaN then, every bin is
+        empty and the result is one "NaN" per NaN row (pandrs_hip.h)."""
+        if k > L.BIN_MAX_BINS:
+            raise InvalidValue("%s takes at most %d, got %d" % (what, L.BIN_MAX_BINS, k))
+        n = c.len()
+        ctx = get_context() if n else None
+        edges, valid = ctx.bin_edges(c.view(), n, kind, k) if n else (None, 0)
+        if valid == 0:
+            raise InvalidValue("No valid values in column" if kind == L.BIN_CUT else "No valid values")
+        if np.isnan(edges[0]):
+            return None, edges, n - valid
+        look = edges.copy()
+        if kind == L.BIN_QCUT:
+            look[k] = edges[k] + 0.001                                   # functions.rs:2406-2407
+        elif look[k] < look[k - 1]:
+            look[k] = look[k - 1]                                        # (for the search only: no row lies between them)
+        codes, _ = ctx.bin(c.view(), n, look, out_device=False, want_counts=False)
+        return np.asarray(codes), edges, n - valid
+
+    def cut(self, column, bins):
+        """PandasCompatExt::cut (functions.rs:2339-2368): `bins` equal-width bins over [min, max] of the cells that are not
+        NaN, the last edge max + 0.001; -> the reference's Vec<String>: "(lo, hi]" with two decimals for the first bin with
+        lo <= v < hi, "NaN" for a NaN or null cell, and NO entry for a row that matches no bin (the maximum once max + 0.001
+        == max, from about 2^43 upward): the list is then shorter than the column, as the reference's is.  One
+        pandrs_hip_bin_edges and one pandrs_hip_bin call; at most `bins` labels are formatted.  InvalidValue for bins == 0 or
+        no valid cell; ColumnNotFound / ColumnTypeMismatch before any device call.  Deviation (pandrs_hip.h): an edge that
+        is zero may read "-0.00"."""
+        c = self._numeric(column)
+        bins = int(bins)
+        if bins <= 0:
+            raise InvalidValue("Number of bins must be > 0")
+        codes, edges, n_nan = self._bin_labels(c, L.BIN_CUT, bins, "cut: bins")
+        if codes is None:
+            return ["NaN"] * n_nan
+        labels = np.empty(bins + 2, dtype=object)                        # code -> label, "NaN" behind the bins; NONE has none
+        for i in np.unique(codes[codes >= 0]):                           # (only the bins that hold a row are formatted)
+            labels[i] = "(%.2f, %.2f]" % (edges[i], edges[i + 1])
+        labels[bins + 1] = "NaN"
+        kept = codes[codes != L.BIN_NONE]
+        return labels[np.where(kept == L.BIN_NAN, bins + 1, kept)].tolist()
+
+    def qcut(self, column, q):
+        """PandasCompatExt::qcut (functions.rs:2370-2420): edges at the order statistics valid[min(m * i / q, m - 1)] of the
+        m cells that are not NaN, the last one + 0.001 for the look-up; -> the reference's Vec<String>: "Q{i + 1}" for the
+        first i with e[i] <= v < e[i + 1], "NaN" for a NaN or null cell, "" for a row that matches no bin.  One
+        pandrs_hip_bin_edges call (the radix select of describe, no sort) and one pandrs_hip_bin call.  InvalidValue for
+        q == 0 or no valid cell; ColumnNotFound / ColumnTypeMismatch before any device call."""
+        c = self._numeric(column)
+        q = int(q)
+        if q <= 0:
+            raise InvalidValue("Number of quantiles must be > 0")
+        codes, _, _ = self._bin_labels(c, L.BIN_QCUT, q, "qcut: q")
+        labels = np.array(["Q%d" % (i + 1) for i in range(q)] + ["", "NaN"], dtype=object)
+        return labels[np.where(codes >= 0, codes, q - 1 - codes)].tolist()
+
     # -- cumulative folds and lags (dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094) ------------
     def _cumulative(self, column_name, op):
         """One pandrs_hip_cumulative call -> the values as a host array.  Errors before any device call: ColumnNotFound,
