@@ -221,6 +221,9 @@ int32_t pandrs_hip_workspace_poisoned_bytes(int64_t *out_bytes);
  *   "bin_path"          tests / experiments: 1 = pandrs_hip_bin always takes the search, 2 = it takes the guess wherever the edges
  *                       are evenly spaced; 0 = the default, the guess from bin_guess_min_bins evenly spaced bins on (the same
  *                       codes; experiments/bin_bench.py)
+ *   "distinct_path"     tests / experiments: 1 = pandrs_hip_distinct takes the direct (LDS table) path wherever the column's numbers fit
+ *                       it, 2 = it always takes the groupby engine; 0 = the default, direct wherever it fits (the same list;
+ *                       experiments/distinct_bench.py)
  *   "window_quantile_path"  tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, which serves rolling
  *                       windows of at most 44 rows (a wider or expanding window: PANDRS_HIP_ERR_INVALID_ARGUMENT), 2 = it always
  *                       takes the general (wavelet matrix) path; 0 = the default, by the window (experiments/window_quantile_bench.py)
@@ -1025,6 +1028,85 @@ int32_t pandrs_hip_bin(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_
  * neither null nor NaN. */
 int32_t pandrs_hip_bin_edges(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind,
                              int32_t k, double *out_edges, int64_t *out_valid);
+
+/* ---- distinct values of one column and their counts: value_counts, unique, nunique, mode, is_unique ------------------------------
+ * PandasCompatExt::unique / value_counts (src/dataframe/pandas_compat/functions.rs:343-384), nunique (:775-788), value_counts_numeric /
+ * unique_numeric (:1709-1753), mode_numeric / mode_string (:4120-4139) and mode_with_count / is_unique / nunique_all (:4226-4259).
+ * Every one of them asks "which values does the column hold, and how often": pandrs_hip_distinct computes that list on the device
+ * and keeps it in the context, pandrs_hip_distinct_fetch copies it out (two steps, as groupby_agg / groupby_fetch: the caller
+ * allocates after it knows n_entries).
+ * Entries: one per distinct number, then at most one NaN entry and one NULL entry.  An entry's value is an 8-byte cell as in
+ * groupby_fetch (the i64, the f64 bits, a zero-extended code, 0 / 1), its flag 0 for a number, 1 for the NaN entry (value: the
+ * canonical NaN 0x7FF8000000000000), 2 for the NULL entry (value 0).  All NaN payloads form one entry; -0.0 and 0.0 are two
+ * entries (the reference keys on to_bits); a cell under a null bit is never looked at and nulls form the one NULL entry (the
+ * engine's key rule, above: "a null key is its own group").  Counts are int64 and exact; they always sum to n_rows, and
+ * n_valid + nan_count + null_count == n_rows.
+ * Order: PANDRS_HIP_DISTINCT_BY_VALUE: numbers ascending in the total order of the order-preserving image of their bits (I64 as
+ * signed integers; F64 -inf .. -0.0, 0.0 .. +inf, so -0.0 before 0.0; BOOLBITS false, true), then the NaN entry, then the NULL
+ * entry.  U32CODE orders by code_rank[code] when code_rank (n_codes uint32, a permutation of 0 .. n_codes: the byte-wise string
+ * order, as pandrs_hip_sort_indices takes it) is given and by code when it is NULL; with n_codes > 0 a code >= n_codes is
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT, found on the device with no fault, and the context serves the next call.
+ * PANDRS_HIP_DISTINCT_BY_COUNT: count descending, ties in the value order above (functions.rs:366, :379-382).  Both orders are
+ * fully determined: a result can be compared bit for bit.
+ * max_count is the largest count among the numbers (0 if there is none) and n_modes how many numbers have it: under BY_COUNT
+ * they need not be the first entries, since a NaN or NULL entry with a larger count comes before them.
+ * Deviations: the reference keeps NaN payloads apart (one entry per payload; here one canonical entry); its order among values
+ * that compare Equal under partial_cmp (NaNs, -0.0 / 0.0, equal counts) is HashMap order (here the total order above); it converts
+ * I64 `as f64` before counting, so integers above 2^53 may merge (here they are counted as i64 and stay apart).
+ * How (distinct.hip): a census stream (16-byte loads) finds min and max, the NaN / null / valid counts and for F64 whether every
+ * number is integral with |v| <= 2^53 and whether a -0.0 is present.  Direct path (info.path 1): when the numbers span at most
+ * distinct_direct_max_cells cells (max - min + 1 in unsigned 64-bit, so I64_MIN .. I64_MAX does not wrap; codes and bools by
+ * value; F64 by (int64)v - min, only when all numbers are integral and no -0.0 is present) a second stream counts into a uint32
+ * table in LDS: lanes of a wave holding the same cell add once by ballot, the rest by LDS atomics, so one hot value does not
+ * serialise; a per-workgroup uint32 counter cannot overflow below 2^32 rows; non-zero cells are added to 64-bit workspace
+ * counters when the workgroup ends, and one small kernel compacts them in ascending order.  8 bytes read per row and stream,
+ * nothing written.  Engine path (info.path 2), everything else: the groupby engine with the column as the key and COUNT (its
+ * doubles are exact below 2^53), its groups turned into entries on the device.  Both: the radix sort of pandrs_hip_sort_indices
+ * orders the entries by (count descending,) class and order key, skipped where the direct table is already in order; a reduce
+ * finds max_count and n_modes.  No workgroup waits for another; every row index is 64-bit.
+ * Geometry (tests read it): distinct_direct_max_cells = 8192 (32 KiB of uint32 counters per 256-thread workgroup, four
+ * workgroups per compute unit inside 160 KiB of LDS); distinct_tile_rows = 2048 rows per workgroup iteration;
+ * distinct_blocks_per_cu = 4; grid = min(distinct_blocks_per_cu x compute units, ceil(n_rows / distinct_tile_rows)).
+ * "distinct_path" (pandrs_hip_ctx_set_option): 0 = default and 1 = direct wherever it is possible, 2 = always the engine; the
+ * same list either way.  pandrs_hip_get_timings: n_partitions reports the path taken (1 direct, 2 engine); the census is
+ * PANDRS_HIP_PHASE_ESTIMATE, the direct stream PANDRS_HIP_PHASE_AGGREGATE.
+ * Retained state: the list stays in the context until the next compute call on it, successful or not (every entry point that
+ * starts a new pandrs_hip_get_timings record; the fetches, key_hash_cells and bytes_to_bitmap do not, and the list has an arena
+ * of its own, so a fetch never serves bytes another call wrote); pandrs_hip_distinct_fetch without a list is
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT, may be repeated, and any of its pointers may be NULL.  A pandrs_hip_distinct call invalidates the retained groupby result (groupby_fetch / partials_split) on
+ * both paths; the engine path also overwrites what pandrs_hip_groupby_agg overwrites: the join result (join_fetch / join_gather).
+ * The grouping of pandrs_hip_groupby_indices, the filter selection and the shuffle buckets stay as they were.
+ * Buffers: a host column and a host code_rank are staged; device and resident columns are read in place.  I64 / F64 data 8-byte
+ * aligned (16 not needed), codes 4-byte aligned, a null mask at any byte offset, bits past n_rows ignored.  out_info is a host
+ * pointer.  The fetch's outputs (in out_mem_space) receive n_entries cells / bytes / int64.
+ * Workspace, sized up front: the census block and distinct_direct_max_cells counters whatever n_rows.  Sized at the stage that
+ * needs them, since they depend on what the column holds: the entry lists (57 bytes per entry) once the entries are counted; on
+ * the engine path groupby_agg's workspace, and for an order that is not skipped the sort's.  A memory_limit below any of them is
+ * PANDRS_HIP_ERR_OUT_OF_MEMORY, which can therefore come after the census or the engine has run (nothing is retained then, and
+ * the context serves the next call).  Every block is written before it is read.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL col
+ * / out_info, a CELL64 column or any other dtype outside I64 / F64 / U32CODE / BOOLBITS, an order outside the enum, code_rank
+ * with another dtype or with n_codes == 0, n_codes < 0, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows ==
+ * 0: OK, an empty list and all-zero info (a call like any other: it starts and ends a timings record).
+ * Out of scope: a call between 2^31 and 2^32 rows is untested (the row arithmetic is 64-bit by construction); per-row codes
+ * (to_categorical), duplicated / drop_duplicates, crosstab; the multi-GPU path. */
+typedef enum pandrs_hip_distinct_order { PANDRS_HIP_DISTINCT_BY_VALUE = 0, PANDRS_HIP_DISTINCT_BY_COUNT = 1 } pandrs_hip_distinct_order;
+
+typedef struct pandrs_hip_distinct_info {
+    int64_t n_entries;    /* entries of the retained list: distinct numbers, then at most one NaN entry and one NULL entry */
+    int64_t n_valid;      /* rows that are neither null nor (F64) NaN */
+    int64_t nan_count, null_count;
+    int64_t max_count;    /* largest count among the non-NaN, non-NULL entries; 0 if none */
+    int64_t n_modes;      /* how many such entries have it */
+    int32_t path;         /* 1 = direct table, 2 = engine */
+    int32_t reserved;
+} pandrs_hip_distinct_info;
+
+int32_t pandrs_hip_distinct(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                            int32_t order, const uint32_t *code_rank, int64_t n_codes, pandrs_hip_distinct_info *out_info);
+/* any pointer may be NULL */
+int32_t pandrs_hip_distinct_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, uint64_t *out_values, uint8_t *out_flags,
+                                  int64_t *out_counts);
 
 /* ---- running folds and lagged differences of one numeric column: cumsum, cumprod, cummax, cummin, cumcount, shift, diff ------
  * PandasCompatExt::cumsum / cumprod / cummax / cummin (src/dataframe/pandas_compat/functions.rs:280-327), shift (:328-342),

@@ -14,6 +14,7 @@
 //                             rank: src/dataframe/pandas_compat/functions.rs:193-236
 //                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
 //                             value_range / cut / qcut: functions.rs:2270-2282, :2339-2420
+//                             value_counts / unique / nunique / mode_* / is_unique: functions.rs:343-384, :775-788, :1709-1753, :4120-4139, :4226-4259
 //                             gt / ge / lt / le / eq_value / ne_value: pandas_compat/helpers/comparison_ops.rs:7-46;
 //                             between / is_between / isna / notna / is_finite / is_infinite / isin / isin_numeric /
 //                             query_* / dropna / count_na / has_nulls / count_value: functions.rs:141-158, :253-257,
@@ -444,6 +445,91 @@ public:
             if (codes[r] == PANDRS_HIP_BIN_NAN) out[r] = "NaN";
             else if (codes[r] >= 0) out[r] = "Q" + std::to_string(codes[r] + 1);
         return out;
+    }
+    // value_counts / unique / nunique / mode / is_unique (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:343-384,
+    // :775-788, :1709-1753, :4120-4139, :4226-4259): one pandrs_hip_distinct call each (the distinct values and their exact counts,
+    // ordered on the device), the list of distinct values assembled on the host.  A missing cell behaves as NaN for a numeric
+    // column (one (NaN, nan_count + null_count) entry, as in cut and fillna) and as "" otherwise.  Deviations (pandrs_hip.h): all
+    // NaN payloads are one entry; -0.0 comes before 0.0 where the reference's order is HashMap order; Int64 cells are counted as
+    // integers; mode_with_count returns the SMALLEST of the numbers that share the largest count (the reference: an arbitrary one).
+    // ColumnNotFound / Type before any device call.
+    std::vector<std::pair<std::string, size_t>> value_counts(const std::string &column_name) const {
+        const Column &c = column(column_name);
+        bool merged = false;
+        auto entries = string_entries(column_name, PANDRS_HIP_DISTINCT_BY_COUNT, &merged);
+        if (merged || c.index() != 2)      // a String column arrives ordered (count descending, then its strings through the rank table)
+            std::stable_sort(entries.begin(), entries.end(), [](const auto &a, const auto &b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });
+        return entries;
+    }
+    std::vector<std::pair<double, size_t>> value_counts_numeric(const std::string &column_name) const {
+        numeric(column_name);
+        const DistinctList d = distinct(column_name, PANDRS_HIP_DISTINCT_BY_COUNT);
+        std::vector<std::pair<double, size_t>> out;
+        const size_t missing = (size_t)(d.info.nan_count + d.info.null_count);
+        bool placed = missing == 0;
+        for (size_t i = 0; i < d.values.size(); i++) {
+            if (d.flags[i]) continue;
+            if (!placed && (size_t)d.counts[i] < missing) { out.emplace_back(std::nan(""), missing); placed = true; }
+            out.emplace_back(cell_f64(column_name, d.values[i]), (size_t)d.counts[i]);
+        }
+        if (!placed) out.emplace_back(std::nan(""), missing);
+        return out;
+    }
+    std::vector<std::string> unique(const std::string &column_name) const {
+        std::vector<std::string> out;
+        for (auto &e : string_entries(column_name, PANDRS_HIP_DISTINCT_BY_VALUE, nullptr)) out.push_back(e.first);
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+    std::vector<double> unique_numeric(const std::string &column_name) const {
+        numeric(column_name);
+        const DistinctList d = distinct(column_name, PANDRS_HIP_DISTINCT_BY_VALUE);
+        std::vector<double> out;
+        for (size_t i = 0; i < d.values.size(); i++)
+            if (!d.flags[i]) out.push_back(cell_f64(column_name, d.values[i]));
+        if (d.info.nan_count + d.info.null_count) out.push_back(std::nan(""));
+        return out;
+    }
+    std::vector<std::pair<std::string, size_t>> nunique() const {
+        std::vector<std::pair<std::string, size_t>> out;
+        for (auto &name : column_names) out.emplace_back(name, string_entries(name, PANDRS_HIP_DISTINCT_BY_VALUE, nullptr).size());
+        return out;
+    }
+    std::unordered_map<std::string, size_t> nunique_all() const {
+        std::unordered_map<std::string, size_t> out;
+        for (auto &name : column_names) out[name] = numbers_of(distinct(name, PANDRS_HIP_DISTINCT_BY_VALUE).info);
+        return out;
+    }
+    std::vector<double> mode_numeric(const std::string &column_name) const {
+        numeric(column_name);
+        const DistinctList d = distinct(column_name, PANDRS_HIP_DISTINCT_BY_VALUE);
+        std::vector<double> out;
+        for (size_t i = 0; i < d.values.size(); i++)
+            if (!d.flags[i] && d.counts[i] == d.info.max_count) out.push_back(cell_f64(column_name, d.values[i]));
+        return out;
+    }
+    std::vector<std::string> mode_string(const std::string &column_name) const {
+        if (column(column_name).index() != 2) throw Error(Error::Type, "Column '" + column_name + "' is not a string type");
+        size_t top = 0;
+        auto entries = string_entries(column_name, PANDRS_HIP_DISTINCT_BY_VALUE, nullptr);
+        for (auto &e : entries)
+            if (!e.first.empty()) top = std::max(top, e.second);
+        std::vector<std::string> out;
+        for (auto &e : entries)
+            if (!e.first.empty() && e.second == top) out.push_back(e.first);
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+    std::pair<double, size_t> mode_with_count(const std::string &column_name) const {
+        numeric(column_name);
+        const DistinctList d = distinct(column_name, PANDRS_HIP_DISTINCT_BY_COUNT);
+        for (size_t i = 0; i < d.values.size(); i++)
+            if (!d.flags[i]) return {cell_f64(column_name, d.values[i]), (size_t)d.counts[i]};      // BY_COUNT: the largest count, then the smallest value
+        return {std::nan(""), 0};
+    }
+    bool is_unique(const std::string &column_name) const {
+        const pandrs_hip_distinct_info info = distinct(column_name, PANDRS_HIP_DISTINCT_BY_VALUE).info;
+        return (int64_t)numbers_of(info) == info.n_valid;
     }
     // cumsum / cumprod / cummax / cummin / cumcount / shift / diff / pct_change (PandasCompatExt,
     // src/dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094): the reference's vectors from one
@@ -1132,6 +1218,58 @@ private:
         detail::check(pandrs_hip_bin(detail::context(), mem_space(), &v, (int64_t)row_count_, look.data(), (int32_t)k, PANDRS_HIP_MEM_HOST,
                                      codes.data(), nullptr));
         return row_count_ - (size_t)valid;
+    }
+    // the list of one pandrs_hip_distinct call; a String column is ordered by its strings (the pool's rank table)
+    struct DistinctList {
+        std::vector<uint64_t> values;
+        std::vector<uint8_t> flags;        // 0 number, 1 the NaN entry, 2 the NULL entry
+        std::vector<int64_t> counts;
+        pandrs_hip_distinct_info info{};
+    };
+    DistinctList distinct(const std::string &name, int32_t order) const {
+        const Column &c = column(name);
+        DistinctList d;
+        if (!row_count_) return d;
+        const pandrs_hip_column v = view_of(name);
+        const bool strings = c.index() == 2;
+        std::vector<uint32_t> rank = strings ? StringPool::global().rank_table() : std::vector<uint32_t>{};
+        const uint32_t *rank_ptr = rank.data();
+        detail::Staged staged_rank;
+        if (strings && is_resident()) rank_ptr = staged_rank.upload(rank);     // one memory space per call
+        detail::check(pandrs_hip_distinct(detail::context(), mem_space(), &v, (int64_t)row_count_, order, strings ? rank_ptr : nullptr,
+                                          (int64_t)rank.size(), &d.info));
+        const size_t n = (size_t)d.info.n_entries;
+        d.values.resize(n); d.flags.resize(n); d.counts.resize(n);
+        detail::check(pandrs_hip_distinct_fetch(detail::context(), PANDRS_HIP_MEM_HOST, d.values.data(), d.flags.data(), d.counts.data()));
+        return d;
+    }
+    static size_t numbers_of(const pandrs_hip_distinct_info &info) {
+        return (size_t)(info.n_entries - (info.nan_count ? 1 : 0) - (info.null_count ? 1 : 0));
+    }
+    double cell_f64(const std::string &name, uint64_t cell) const {      // an entry of a numeric column as the reference's f64
+        if (column(name).index() == 0) return (double)(int64_t)cell;
+        double d;
+        std::memcpy(&d, &cell, 8);
+        return d;
+    }
+    // [(string, count)] in the device's order: the strings get_column_string_values gives; the missing cells as "NaN" (numeric)
+    // or "", merged with such an entry of the column's own
+    std::vector<std::pair<std::string, size_t>> string_entries(const std::string &name, int32_t order, bool *merged) const {
+        const int32_t dtype = detail::col_dtype(column(name));
+        const DistinctList d = distinct(name, order);
+        std::vector<std::pair<std::string, size_t>> out;
+        size_t missing = 0;
+        for (size_t i = 0; i < d.values.size(); i++) {
+            if (d.flags[i]) missing += (size_t)d.counts[i];
+            else out.emplace_back(detail::key_string(dtype, d.values[i], false), (size_t)d.counts[i]);
+        }
+        if (merged) *merged = missing != 0;
+        if (!missing) return out;
+        const std::string as = dtype <= PANDRS_HIP_F64 ? "NaN" : "";
+        for (auto &e : out)
+            if (e.first == as) { e.second += missing; return out; }
+        out.emplace_back(as, missing);
+        return out;
     }
     pandrs_hip_column_stats stats(const std::string &name) const {
         const Column &c = column(name);

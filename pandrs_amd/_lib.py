@@ -37,6 +37,8 @@ EVAL_COL, EVAL_CONST, EVAL_ADD, EVAL_SUB, EVAL_MUL, EVAL_DIV, EVAL_REM, EVAL_MAX
 EVAL_MAX_OPS, EVAL_MAX_COLS, EVAL_MAX_DEPTH = 64, 8, 8
 BIN_CUT, BIN_QCUT = range(2)
 BIN_NONE, BIN_NAN, BIN_MAX_BINS = -1, -2, 4096
+DISTINCT_BY_VALUE, DISTINCT_BY_COUNT = range(2)
+DISTINCT_NUMBER, DISTINCT_NAN, DISTINCT_NULL = range(3)        # the flags of a distinct entry
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -82,6 +84,11 @@ class WindowQuantileSpec(C.Structure):     # pandrs_hip_window_quantile_spec
 class DescribeStats(C.Structure):          # pandrs_hip_describe_stats
     _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("q1", C.c_double),
                 ("median", C.c_double), ("q3", C.c_double), ("max", C.c_double)]
+
+
+class DistinctInfo(C.Structure):           # pandrs_hip_distinct_info
+    _fields_ = [("n_entries", C.c_int64), ("n_valid", C.c_int64), ("nan_count", C.c_int64), ("null_count", C.c_int64),
+                ("max_count", C.c_int64), ("n_modes", C.c_int64), ("path", C.c_int32), ("reserved", C.c_int32)]
 
 
 # pandrs_hip_transport: the exchange's collectives as host callbacks (pandrs_hip_comm_adopt_transport)
@@ -184,6 +191,8 @@ SYMBOLS = {
                                    C.POINTER(C.c_int64)]),
     "pandrs_hip_bin_edges": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                          C.POINTER(C.c_int64)]),
+    "pandrs_hip_distinct": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(DistinctInfo)]),
+    "pandrs_hip_distinct_fetch": (C.c_int32, [_P, C.c_int32, _P, _P, _P]),
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -98,7 +98,7 @@ int32_t pandrs_hip_ctx_destroy(pandrs_hip_ctx *c) try {
     if (!c) return PANDRS_HIP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release(); c->topk.release();
+    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release(); c->topk.release(); c->dn_arena.release();
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) { (void)hipEventDestroy(c->ev_begin[i]); (void)hipEventDestroy(c->ev_end[i]); }
     (void)hipEventDestroy(c->ev_call_begin); (void)hipEventDestroy(c->ev_call_end);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -263,6 +263,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "isin_path")) c->opt.isin_path = value;
     else if (!std::strcmp(name, "predicate_path")) c->opt.predicate_path = value;
     else if (!std::strcmp(name, "bin_path")) c->opt.bin_path = value;
+    else if (!std::strcmp(name, "distinct_path")) c->opt.distinct_path = value;
     else if (!std::strcmp(name, "window_quantile_path")) c->opt.window_quantile_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
@@ -599,6 +600,19 @@ int32_t pandrs_hip_bin_edges(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
     ST_TRY(pandrs::below_threshold(n_rows));
     return pandrs::bin_edges_entry(ctx, mem_space, col, n_rows, kind, k, out_edges, out_valid);
 } catch (...) { return pandrs::on_exception("pandrs_hip_bin_edges"); }
+
+int32_t pandrs_hip_distinct(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t order,
+                            const uint32_t *code_rank, int64_t n_codes, pandrs_hip_distinct_info *out_info) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "distinct: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::distinct_entry(ctx, mem_space, col, n_rows, order, code_rank, n_codes, out_info);
+} catch (...) { return pandrs::on_exception("pandrs_hip_distinct"); }
+
+int32_t pandrs_hip_distinct_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, uint64_t *out_values, uint8_t *out_flags,
+                                  int64_t *out_counts) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "distinct_fetch: no context");
+    return pandrs::distinct_fetch_entry(ctx, out_mem_space, out_values, out_flags, out_counts);
+} catch (...) { return pandrs::on_exception("pandrs_hip_distinct_fetch"); }
 
 int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
                         const int32_t *ops, const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,

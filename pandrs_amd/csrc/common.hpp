@@ -205,6 +205,16 @@ struct FilterResult {
     uint32_t *offs = nullptr;    // [n_tiles + 1]
 };
 
+// the list of the last pandrs_hip_distinct (distinct.hip), in the `dn_arena`: entry values, flags (0 number, 1 NaN, 2 NULL), counts
+// (retained "until the next compute call", pandrs_hip.h: timings_begin, where every compute call starts, drops it)
+struct DistinctResult {
+    bool valid = false;
+    int64_t n_entries = 0;
+    uint64_t *values = nullptr;
+    uint8_t *flags = nullptr;
+    int64_t *counts = nullptr;
+};
+
 struct Options {
     int64_t groups_hint = 0;     // 0 = estimate from a sample
     int64_t scatter_staged = 1;  // stage columns through LDS for coalesced partition writes
@@ -258,6 +268,7 @@ struct Options {
     int64_t isin_path = 0;           // tests / experiments: 1 = pandrs_hip_isin takes the LDS set wherever the list fits, 2 = always the global set (0 = by the list's size)
     int64_t predicate_path = 0;      // tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in the loop instead of comparing integers against the bisected interval
     int64_t bin_path = 0;            // tests / experiments: 1 = pandrs_hip_bin always searches, 2 = it guesses wherever the edges are evenly spaced (0 = the guess from bin_guess_min_bins bins on)
+    int64_t distinct_path = 0;       // tests / experiments: 1 = pandrs_hip_distinct takes the direct (LDS table) path wherever the numbers fit it, 2 = always the engine (0 = direct wherever it fits)
     int64_t window_quantile_path = 0;   // tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, 2 = the general (wavelet matrix) path (0 = by the window)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
@@ -312,6 +323,8 @@ struct pandrs_hip_ctx {
     bool test_throw_nested = false;   // set_option("test_throw", 5): the next nested engine run throws std::bad_alloc, once
     int lds_bytes = 0;           // usable LDS per workgroup
     int n_cu = 0;
+    pandrs::Arena dn_arena;      // the retained distinct list and its unsorted form (distinct.hip)
+    pandrs::DistinctResult dn;
 };
 
 namespace pandrs {
@@ -329,7 +342,9 @@ struct PhaseTimer {
     ~PhaseTimer() { if (!c->quiet) (void)hipEventRecord(c->ev_end[phase], c->stream); }
 };
 
+// (every compute call begins here: the distinct list is retained "until the next compute call", pandrs_hip.h)
 inline void timings_begin(pandrs_hip_ctx *c) {
+    c->dn.valid = false;
     std::memset(&c->timings, 0, sizeof c->timings);
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) c->ev_used[i] = false;
     c->timings_lazy = c->timings_pending = false;
@@ -417,6 +432,10 @@ int32_t bin_edges_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_c
 // bin.hip: per row the i with edges[i] <= v < edges[i + 1] (or PANDRS_HIP_BIN_NONE / PANDRS_HIP_BIN_NAN), and the rows per code
 int32_t bin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *edges, int32_t n_bins,
                   int32_t out_mem_space, int32_t *out_codes, int64_t *out_counts);
+// distinct.hip: the distinct values of a column with their counts, ordered by value or by count; retained in c->dn for the fetch
+int32_t distinct_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t order,
+                       const uint32_t *code_rank, int64_t n_codes, pandrs_hip_distinct_info *out_info);
+int32_t distinct_fetch_entry(pandrs_hip_ctx *c, int32_t out_mem_space, uint64_t *out_values, uint8_t *out_flags, int64_t *out_counts);
 // rank.hip: the ascending 1-based rank of every row (method = pandrs_hip_rank_method), NaN for NaN and null cells
 int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method,
                    int32_t out_mem_space, double *out);

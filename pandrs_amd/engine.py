@@ -1202,6 +1202,57 @@ class Context:
             _raise(st)
         return (None if out is None else out[:n]), (counts if want_counts else None)
 
+    # -- distinct values and their counts (an LDS table for few distinct integers, else the groupby engine) ----------------
+    def distinct(self, col, n_rows, order, code_rank=None, out_device=False):
+        """The distinct values of one I64 / F64 / U32CODE / BOOLBITS column and how often each occurs, on the device
+        (pandrs_hip_distinct + pandrs_hip_distinct_fetch; PandasCompatExt::value_counts / unique / nunique / mode,
+        src/dataframe/pandas_compat/functions.rs:343-384, :1709-1753, :4120-4139).  `col` is a (data, mask, dtype) triple on the
+        host or the device, or a ResidentColumn; `order` L.DISTINCT_BY_VALUE (numbers ascending, -0.0 before 0.0, then the NaN
+        entry, then the NULL entry) or L.DISTINCT_BY_COUNT (count descending, ties in that order); `code_rank` the string
+        pool's rank table, which makes a U32CODE column order by its strings instead of its codes.
+        -> (values, flags, counts, info): uint64 cells (the i64, the f64 bits, the code, 0 / 1), uint8 flags (L.DISTINCT_NUMBER,
+        L.DISTINCT_NAN, L.DISTINCT_NULL), exact int64 counts - numpy arrays, or with out_device torch tensors on this context's
+        device (values as int64 bit patterns) - and the L.DistinctInfo of the call as a dict."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        rank, n_codes = None, 0
+        if code_rank is not None:
+            if sp == L.MEM_DEVICE:
+                import torch
+                rank = code_rank if _is_torch(code_rank) else torch.from_numpy(
+                    np.ascontiguousarray(code_rank, dtype=np.uint32).view(np.int32)).to("cuda:%d" % self.device)
+                if _is_torch(code_rank):
+                    self._wait_for_producer()
+            else:
+                rank = np.ascontiguousarray(code_rank.cpu().numpy() if _is_torch(code_rank) else code_rank).view(np.uint32)
+            keep.append(rank)
+            n_codes = int(rank.numel() if _is_torch(rank) else rank.shape[0])
+        info = L.DistinctInfo()
+        st = self.lib.pandrs_hip_distinct(self.h, sp, cc, int(n_rows), int(order), _ptr(rank), n_codes, C.byref(info))
+        if st:
+            _raise(st)
+        values, flags, counts = self.distinct_fetch(info.n_entries, out_device)
+        return values, flags, counts, {name: getattr(info, name) for name, _ in L.DistinctInfo._fields_ if name != "reserved"}
+
+    def distinct_fetch(self, n_entries, out_device=False, values=True, flags=True, counts=True):
+        """The list the last distinct call left in the context (until the next compute call on it), or the parts asked for."""
+        n = int(n_entries)
+        if out_device:
+            import torch
+            dev = "cuda:%d" % self.device
+            v = torch.empty(n, dtype=torch.int64, device=dev) if values else None
+            f = torch.empty(n, dtype=torch.uint8, device=dev) if flags else None
+            k = torch.empty(n, dtype=torch.int64, device=dev) if counts else None
+        else:
+            v = np.empty(n, np.uint64) if values else None
+            f = np.empty(n, np.uint8) if flags else None
+            k = np.empty(n, np.int64) if counts else None
+        st = self.lib.pandrs_hip_distinct_fetch(self.h, L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(v) if n else None,
+                                                _ptr(f) if n else None, _ptr(k) if n else None)
+        if st:
+            _raise(st)
+        return v, f, k
+
     # -- derived columns (one postfix program over up to eight columns, one stream) ---------------------------------------
     @staticmethod
     def eval_check(dtypes, program):

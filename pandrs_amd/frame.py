@@ -858,6 +858,142 @@ class OptimizedDataFrame:
         labels = np.array(["Q%d" % (i + 1) for i in range(q)] + ["", "NaN"], dtype=object)
         return labels[np.where(codes >= 0, codes, q - 1 - codes)].tolist()
 
+    # -- value_counts / unique / nunique / mode / is_unique (dataframe/pandas_compat/functions.rs:343-384, :775-788, -------
+    #    :1709-1753, :4120-4139, :4226-4259): one pandrs_hip_distinct call each, the list of distinct values on the host ----
+    def _distinct(self, col, order):
+        """-> (values, flags, counts, info) of one pandrs_hip_distinct call; a String column orders by its strings (the pool's
+        rank table).  No rows: an empty list, no device call."""
+        n = col.len()
+        if n == 0:
+            return (np.empty(0, np.uint64), np.empty(0, np.uint8), np.empty(0, np.int64),
+                    {"n_entries": 0, "n_valid": 0, "nan_count": 0, "null_count": 0, "max_count": 0, "n_modes": 0, "path": 0})
+        rank = GLOBAL_STRING_POOL.rank_table() if col.dtype == L.U32CODE else None
+        v, f, k, info = get_context().distinct(col.view(), n, order, code_rank=rank, out_device=False)
+        return np.asarray(v, np.uint64), np.asarray(f, np.uint8), np.asarray(k, np.int64), info
+
+    @staticmethod
+    def _cells_as_f64(col, values):
+        """Entry cells of a numeric column as the reference's f64 values (an Int64 cell `as f64`)."""
+        if col.dtype == L.F64:
+            return values.view(np.float64)
+        return values.view(np.int64).astype(np.float64)
+
+    def _string_entries(self, col, order):
+        """-> [(string, count)] in the device's order: the strings get_column_string_values gives for the column (an Int64 /
+        Float64 cell's to_string, "true" / "false"), a missing cell as "NaN" for a numeric column and as "" otherwise - merged
+        with the "" / "NaN" the column may hold itself.  `merged` says whether an entry's count changed on the host."""
+        v, f, k, _ = self._distinct(col, order)
+        number = f == L.DISTINCT_NUMBER
+        strings = _key_strings(col.dtype, v[number], np.zeros(int(number.sum()), np.uint8))
+        entries = list(zip(strings, k[number].tolist()))
+        missing = int(k[~number].sum())
+        if not missing:
+            return entries, False
+        name = "NaN" if col.dtype in (L.I64, L.F64) else ""
+        for i, (s, c) in enumerate(entries):
+            if s == name:
+                entries[i] = (s, c + missing)
+                return entries, True
+        entries.append((name, missing))
+        return entries, True
+
+    def _string_typed(self, column):
+        col = self.column(column)
+        if col.dtype != L.U32CODE:
+            raise ColumnTypeMismatch(L.ERR_TYPE_MISMATCH, "Column '%s' is not a string type" % column)
+        return col
+
+    def value_counts(self, column):
+        """PandasCompatExt::value_counts (functions.rs:359-368): [(string, count)], count descending, ties by string (byte-wise)
+        - for a String column the device's own order (pandrs_hip_distinct BY_COUNT through the pool's rank table); any other
+        column is counted by value and its entries ordered by their strings on the host, as the reference stringifies first.
+        A missing cell counts as "" (String, Boolean) or "NaN" (numeric).  ColumnNotFound before any device call."""
+        col = self.column(column)
+        entries, merged = self._string_entries(col, L.DISTINCT_BY_COUNT)
+        if merged or col.dtype != L.U32CODE:
+            entries.sort(key=lambda e: (-e[1], e[0].encode()))
+        return entries
+
+    def value_counts_numeric(self, column):
+        """PandasCompatExt::value_counts_numeric (functions.rs:369-384): [(f64, count)], count descending, ties by value.  One
+        (NaN, nan_count + null_count) entry for the NaN and null cells together, after the numbers of its count.  Deviations
+        (pandrs_hip.h): every NaN payload is one entry; -0.0 comes before 0.0 among equal counts (the reference: HashMap
+        order); Int64 cells are counted as integers (beyond 2^53 two entries may print as the same float).  ColumnNotFound /
+        ColumnTypeMismatch before any device call."""
+        col = self._numeric(column)
+        v, f, k, info = self._distinct(col, L.DISTINCT_BY_COUNT)
+        number = f == L.DISTINCT_NUMBER
+        out = list(zip(self._cells_as_f64(col, v[number]).tolist(), k[number].tolist()))
+        missing = info["nan_count"] + info["null_count"]
+        if missing:
+            at = int(np.searchsorted(-k[number], -missing, side="right"))
+            out.insert(at, (math.nan, missing))
+        return out
+
+    def unique(self, column):
+        """PandasCompatExt::unique (functions.rs:775-781): the column's distinct strings, ascending byte-wise."""
+        col = self.column(column)
+        entries, _ = self._string_entries(col, L.DISTINCT_BY_VALUE)
+        return sorted((s for s, _ in entries), key=str.encode)         # (a String column arrives in this order already)
+
+    def unique_numeric(self, column):
+        """PandasCompatExt::unique_numeric (functions.rs:782-788): the distinct values ascending, -0.0 before 0.0, one NaN last
+        when a cell is NaN or null (the reference: every payload, wherever its sort leaves them)."""
+        col = self._numeric(column)
+        v, f, _, info = self._distinct(col, L.DISTINCT_BY_VALUE)
+        out = self._cells_as_f64(col, v[f == L.DISTINCT_NUMBER]).tolist()
+        return out + ([math.nan] if info["nan_count"] + info["null_count"] else [])
+
+    def nunique(self):
+        """PandasCompatExt::nunique (functions.rs:343-352): [(column, number of distinct strings)] for every column, a missing
+        cell as in value_counts."""
+        return [(name, len(self._string_entries(self.column(name), L.DISTINCT_BY_VALUE)[0])) for name in self.column_names]
+
+    def nunique_all(self):
+        """PandasCompatExt::nunique_all (functions.rs:4120-4139): {column: distinct values}; NaN and missing cells are left out."""
+        out = {}
+        for name in self.column_names:
+            info = self._distinct(self.column(name), L.DISTINCT_BY_VALUE)[3]
+            out[name] = info["n_entries"] - (1 if info["nan_count"] else 0) - (1 if info["null_count"] else 0)
+        return out
+
+    def mode_numeric(self, column):
+        """PandasCompatExt::mode_numeric (functions.rs:1709-1730): the numbers with the largest count, ascending; [] when the
+        column holds no number."""
+        col = self._numeric(column)
+        v, f, k, info = self._distinct(col, L.DISTINCT_BY_VALUE)
+        keep = (f == L.DISTINCT_NUMBER) & (k == info["max_count"])
+        return self._cells_as_f64(col, v[keep]).tolist() if info["max_count"] else []
+
+    def mode_string(self, column):
+        """PandasCompatExt::mode_string (functions.rs:1732-1753): the strings with the largest count, ascending; the "" entry
+        (and with it every missing cell) is dropped first."""
+        col = self._string_typed(column)
+        entries = [(s, c) for s, c in self._string_entries(col, L.DISTINCT_BY_VALUE)[0] if s != ""]
+        if not entries:
+            return []
+        top = max(c for _, c in entries)
+        return sorted((s for s, c in entries if c == top), key=str.encode)
+
+    def mode_with_count(self, column):
+        """PandasCompatExt::mode_with_count (functions.rs:4243-4259): (the most frequent number, its count); (NaN, 0) when
+        there is no number.  Among numbers of the same count this returns the SMALLEST (the reference: whichever its HashMap
+        iterates last)."""
+        col = self._numeric(column)
+        v, f, k, info = self._distinct(col, L.DISTINCT_BY_COUNT)
+        number = np.flatnonzero(f == L.DISTINCT_NUMBER)
+        if number.size == 0:
+            return (math.nan, 0)
+        first = number[:1]                                               # BY_COUNT: the largest count, then the smallest value
+        return (float(self._cells_as_f64(col, v[first])[0]), int(k[first][0]))
+
+    def is_unique(self, column):
+        """PandasCompatExt::is_unique (functions.rs:4226-4241): no value occurs twice among the cells that are neither NaN nor
+        missing."""
+        info = self._distinct(self.column(column), L.DISTINCT_BY_VALUE)[3]
+        numbers = info["n_entries"] - (1 if info["nan_count"] else 0) - (1 if info["null_count"] else 0)
+        return numbers == info["n_valid"]
+
     # -- cumulative folds and lags (dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094) ------------
     def _cumulative(self, column_name, op):
         """One pandrs_hip_cumulative call -> the values as a host array.  Errors before any device call: ColumnNotFound,
