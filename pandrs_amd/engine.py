@@ -11,6 +11,10 @@ import numpy as np
 from . import _lib as L
 
 _NP_OF = {L.I64: np.int64, L.F64: np.float64, L.U32CODE: np.uint32, L.BOOLBITS: np.uint8, L.CELL64: np.uint64}
+# numpy dtype -> the torch dtype (by name: torch is imported lazily) that holds its bits on the device; unsigned 64- and
+# 32-bit cells travel as the signed type of the same width
+_TORCH_OF = {np.int64: "int64", np.uint64: "int64", np.float64: "float64", np.int32: "int32", np.uint32: "int32",
+             np.uint8: "uint8"}
 
 
 class PandrsHipError(RuntimeError):
@@ -50,6 +54,12 @@ def _raise(status):
     raise PandrsHipError(status, msg)
 
 
+def _check(st):
+    """Every C call returns a status; anything but 0 becomes the exception of its code."""
+    if st:
+        _raise(st)
+
+
 def _is_torch(x):
     return x is not None and type(x).__module__.startswith("torch")
 
@@ -60,6 +70,15 @@ def _ptr(x):
     if _is_torch(x):
         return x.data_ptr()
     return x.ctypes.data
+
+
+def _space(on_device):
+    return L.MEM_DEVICE if on_device else L.MEM_HOST
+
+
+def _fill_bits(fill, dtype):
+    """The 64-bit cell that stands for `fill`: the f64's bits for an F64 column, else the integer's low 64 bits."""
+    return int(np.float64(fill).view(np.uint64)) if dtype == L.F64 else int(fill) & 0xFFFFFFFFFFFFFFFF
 
 
 class ResidentColumn:
@@ -75,8 +94,7 @@ class ResidentColumn:
         if self.desc is not None and getattr(self.ctx, "h", None):
             st = self.ctx.lib.pandrs_hip_column_release(self.ctx.h, C.byref(self.desc))
             self.desc = None
-            if st:
-                _raise(st)
+            _check(st)
         self.desc = None
 
     def __iter__(self):        # unpacks like a triple: (self, None, dtype)
@@ -93,9 +111,7 @@ class Context:
     def __init__(self, device=0):
         self.lib = L.load()
         h = C.c_void_p()
-        st = self.lib.pandrs_hip_ctx_create(int(device), C.byref(h))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_ctx_create(int(device), C.byref(h)))
         self.h = h
         self.device = device
         self.grouping_token = 0     # bumped by every groupby_indices: whose grouping the context retains (see grouped)
@@ -149,6 +165,13 @@ class Context:
             self._wait_for_producer()
         return arr, (space if space is not None else L.MEM_HOST)
 
+    def _col(self, col):
+        """One column through _cols.  -> (Column array, memory space, keep): `keep` holds what the array's pointers point
+        into, so the caller keeps it referenced until its C call has returned."""
+        keep = []
+        cc, sp = self._cols([tuple(col)], keep)
+        return cc, sp, keep
+
     def _wait_for_producer(self):
         """The library runs on its own non-blocking stream and (like any C ABI over raw device
         pointers) requires its device inputs to be complete when the call starts.  Tensors handed
@@ -162,6 +185,89 @@ class Context:
         for i, (c, op) in enumerate(aggs):
             arr[i].col, arr[i].op = int(c), int(op)
         return arr
+
+    def _empty(self, shape, np_dtype, device):
+        """Uninitialised storage for a result: a numpy array, or with `device` a torch tensor on this context's GPU."""
+        if not device:
+            return np.empty(shape, np_dtype)
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, _TORCH_OF[np_dtype]), device="cuda:%d" % self.device)
+
+    def _made(self, count, np_dtype, device):
+        """A result buffer of the wrapper's own for `count` cells: exact on the host; on the device at least one cell,
+        sliced to count."""
+        if device:
+            return self._empty(max(count, 1), np_dtype, True)[:count]
+        return self._empty(count, np_dtype, False)
+
+    def _given(self, out, count, np_dtype, what, name="out"):
+        """Checks a caller's result buffer for `count` cells of `np_dtype` (`what` names the count in the error).
+        -> whether it lives on the device."""
+        device = _is_torch(out)
+        if device:
+            import torch
+            ok = out.dtype == getattr(torch, _TORCH_OF[np_dtype]) and out.is_contiguous() and out.is_cuda and out.numel() >= count
+        else:
+            ok = isinstance(out, np.ndarray) and out.dtype == np_dtype and out.flags.c_contiguous and out.size >= count
+        if not ok:
+            raise ValueError("%s must be a contiguous %s numpy array or CUDA tensor of at least %s elements"
+                             % (name, np.dtype(np_dtype).name, what))
+        return device
+
+    def _out_buffer(self, count, np_dtype, sp, out, out_device, what):
+        """Where a call writes `count` cells of `np_dtype`.  -> (buffer of exactly count cells, lives on the device).
+        A caller's `out` decides the space and comes back as a view of its first cells, once it has been checked and, for
+        a CUDA tensor, torch's stream has been waited for.  Else out_device decides, else the space `sp` of the input."""
+        if out is not None:
+            out_device = self._given(out, count, np_dtype, what)
+            if out_device:
+                self._wait_for_producer()
+            return out[:count], out_device
+        if out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        return self._made(count, np_dtype, out_device), out_device
+
+    def _cell_outs(self, n, sp, want_i64, out, out_mask, out_device):
+        """The (out, out_mask, out_device) a call with one 8-byte cell per row and a null bitmap writes into: as
+        _out_buffer for each, but the two share one space and one wait, and both are checked before either is made."""
+        cell, nbytes = (np.int64 if want_i64 else np.float64), (n + 7) // 8
+        if out is not None or out_mask is not None:
+            if out is not None and out_mask is not None and _is_torch(out) != _is_torch(out_mask):
+                raise ValueError("out and out_mask must both be numpy arrays or both CUDA tensors")
+            if out is not None:
+                out_device = self._given(out, n, cell, "n_rows")
+            if out_mask is not None:
+                out_device = self._given(out_mask, nbytes, np.uint8, "ceil(n_rows / 8)", "out_mask")
+            if out_device:
+                self._wait_for_producer()
+        elif out_device is None:
+            out_device = sp == L.MEM_DEVICE
+        out = self._made(n, cell, out_device) if out is None else out[:n]
+        out_mask = self._made(nbytes, np.uint8, out_device) if out_mask is None else out_mask[:nbytes]
+        return out, out_mask, out_device
+
+    def _mask_out(self, n, sp, out, out_device, count_only):
+        """The out_bits buffer of predicate / isin: -> (buffer or None, lives on the device)."""
+        if count_only:
+            if out is not None:
+                raise ValueError("count_only takes no out")
+            return None, False
+        return self._out_buffer((n + 7) // 8, np.uint8, sp, out, out_device, "ceil(n_rows / 8)")
+
+    def _code_rank(self, code_rank, sp, keep):
+        """A string pool's rank table in the memory space `sp` of the call.  -> (table or None, n_codes)"""
+        if code_rank is None:
+            return None, 0
+        if sp != L.MEM_DEVICE:
+            rank = np.ascontiguousarray(code_rank.cpu().numpy() if _is_torch(code_rank) else code_rank).view(np.uint32)
+        elif _is_torch(code_rank):
+            rank = code_rank
+            self._wait_for_producer()
+        else:
+            import torch
+            rank = torch.from_numpy(np.ascontiguousarray(code_rank, dtype=np.uint32).view(np.int32)).to("cuda:%d" % self.device)
+        keep.append(rank)
+        return rank, int(rank.numel() if _is_torch(rank) else rank.shape[0])
 
     # -- resident columns -------------------------------------------------------------------------
     def upload_column(self, data, mask, dtype):
@@ -177,38 +283,26 @@ class Context:
     def upload_column_n(self, data, mask, dtype, n_rows):
         host = L.Column(_ptr(data), _ptr(mask), int(dtype), 0)
         dev = L.Column()
-        st = self.lib.pandrs_hip_column_upload(self.h, C.byref(host), int(n_rows), C.byref(dev))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_column_upload(self.h, C.byref(host), int(n_rows), C.byref(dev)))
         return ResidentColumn(self, dev, int(n_rows))
 
     def resident_bytes(self):
         b, n = C.c_int64(0), C.c_int64(0)
-        st = self.lib.pandrs_hip_resident_bytes(self.h, C.byref(b), C.byref(n))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_resident_bytes(self.h, C.byref(b), C.byref(n)))
         return b.value, n.value
 
     def synchronize(self):
-        st = self.lib.pandrs_hip_ctx_synchronize(self.h)
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_ctx_synchronize(self.h))
 
     def set_option(self, name, value):
-        st = self.lib.pandrs_hip_ctx_set_option(self.h, name.encode(), int(value))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_ctx_set_option(self.h, name.encode(), int(value)))
 
     def reserve(self, nbytes):
-        st = self.lib.pandrs_hip_ctx_reserve(self.h, int(nbytes))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_ctx_reserve(self.h, int(nbytes)))
 
     def timings(self):
         t = L.Timings()
-        st = self.lib.pandrs_hip_get_timings(self.h, C.byref(t))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_get_timings(self.h, C.byref(t)))
         return {
             "total_ms": t.total_ms,
             "phase_ms": {L.PHASE_NAMES[i]: t.phase_ms[i] for i in range(L.MAX_PHASES)
@@ -227,10 +321,8 @@ class Context:
         if vals and sp1 != sp2:
             raise ValueError("keys and values must live in the same memory space")
         ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_groupby_agg(self.h, sp1, kc, len(keys), int(n_rows), vc, len(vals),
-                                             self._aggs(aggs), len(aggs), C.byref(ng))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_groupby_agg(self.h, sp1, kc, len(keys), int(n_rows), vc, len(vals),
+                                               self._aggs(aggs), len(aggs), C.byref(ng)))
         self._last = (len(keys), len(aggs), sp1, ng.value)
         return ng.value
 
@@ -238,24 +330,13 @@ class Context:
         """-> (key_cells[n_keys, G] u64, key_null[n_keys, G] u8, aggs[n_aggs, G] f64)."""
         n_keys, n_aggs, space, g = self._last
         dev = space == L.MEM_DEVICE if to_device is None else to_device
-        if dev:
-            import torch
-            d = "cuda:%d" % self.device
-            kc = torch.empty((n_keys, g), dtype=torch.int64, device=d)
-            kn = torch.empty((n_keys, g), dtype=torch.uint8, device=d)
-            oa = torch.empty((n_aggs, g), dtype=torch.float64, device=d)
-            row = lambda t, i: t[i].data_ptr()
-        else:
-            kc = np.empty((n_keys, g), np.uint64)
-            kn = np.empty((n_keys, g), np.uint8)
-            oa = np.empty((n_aggs, g), np.float64)
-            row = lambda t, i: t[i].ctypes.data
-        pk = (C.c_void_p * max(n_keys, 1))(*[row(kc, i) for i in range(n_keys)])
-        pn = (C.c_void_p * max(n_keys, 1))(*[row(kn, i) for i in range(n_keys)])
-        pa = (C.c_void_p * max(n_aggs, 1))(*[row(oa, i) for i in range(n_aggs)])
-        st = self.lib.pandrs_hip_groupby_fetch(self.h, L.MEM_DEVICE if dev else L.MEM_HOST, pk, pn, pa)
-        if st:
-            _raise(st)
+        kc = self._empty((n_keys, g), np.uint64, dev)
+        kn = self._empty((n_keys, g), np.uint8, dev)
+        oa = self._empty((n_aggs, g), np.float64, dev)
+        pk = (C.c_void_p * max(n_keys, 1))(*[_ptr(kc[i]) for i in range(n_keys)])
+        pn = (C.c_void_p * max(n_keys, 1))(*[_ptr(kn[i]) for i in range(n_keys)])
+        pa = (C.c_void_p * max(n_aggs, 1))(*[_ptr(oa[i]) for i in range(n_aggs)])
+        _check(self.lib.pandrs_hip_groupby_fetch(self.h, _space(dev), pk, pn, pa))
         return kc, kn, oa
 
     def groupby_agg(self, keys, n_rows, vals, aggs):
@@ -270,9 +351,7 @@ class Context:
         kc, sp = self._cols(keys, keep)
         ng = C.c_int64(0)
         self.grouping_token += 1                        # (a failed call drops the retained grouping too)
-        st = self.lib.pandrs_hip_groupby_indices(self.h, sp, kc, len(keys), int(n_rows), C.byref(ng))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_groupby_indices(self.h, sp, kc, len(keys), int(n_rows), C.byref(ng)))
         return ng.value, sp
 
     def groupby_indices(self, keys, n_rows):
@@ -280,26 +359,14 @@ class Context:
         -> (key_cells[n_keys, G] u64, key_null[n_keys, G] u8, offsets[G + 1] i64, rows[n_rows] i64);
         group g = rows[offsets[g]:offsets[g + 1]], ascending."""
         g, sp = self.groupby_indices_compute(keys, n_rows)
-        nk = len(keys)
-        if sp == L.MEM_DEVICE:
-            import torch
-            d = "cuda:%d" % self.device
-            cells = torch.empty((nk, g), dtype=torch.int64, device=d)
-            nulls = torch.empty((nk, g), dtype=torch.uint8, device=d)
-            off = torch.empty(g + 1, dtype=torch.int64, device=d)
-            rows = torch.empty(int(n_rows), dtype=torch.int64, device=d)
-            row = lambda t, i: t[i].data_ptr()
-        else:
-            cells = np.empty((nk, g), np.uint64)
-            nulls = np.empty((nk, g), np.uint8)
-            off = np.empty(g + 1, np.int64)
-            rows = np.empty(int(n_rows), np.int64)
-            row = lambda t, i: t[i].ctypes.data
-        pk = (C.c_void_p * nk)(*[row(cells, i) for i in range(nk)])
-        pn = (C.c_void_p * nk)(*[row(nulls, i) for i in range(nk)])
-        st = self.lib.pandrs_hip_groupby_indices_fetch(self.h, sp, pk, pn, _ptr(off), _ptr(rows))
-        if st:
-            _raise(st)
+        nk, dev = len(keys), sp == L.MEM_DEVICE
+        cells = self._empty((nk, g), np.uint64, dev)
+        nulls = self._empty((nk, g), np.uint8, dev)
+        off = self._empty(g + 1, np.int64, dev)
+        rows = self._empty(int(n_rows), np.int64, dev)
+        pk = (C.c_void_p * nk)(*[_ptr(cells[i]) for i in range(nk)])
+        pn = (C.c_void_p * nk)(*[_ptr(nulls[i]) for i in range(nk)])
+        _check(self.lib.pandrs_hip_groupby_indices_fetch(self.h, sp, pk, pn, _ptr(off), _ptr(rows)))
         return cells, nulls, off, rows
 
     def groupby_agg_chunked(self, keys, n_rows, vals, aggs, chunk_rows):
@@ -346,60 +413,36 @@ class Context:
             raise ValueError("key and payload must live in the same memory space")
         counts = (C.c_int64 * n_ranks)()
         n_out = C.c_int64(0)
-        st = self.lib.pandrs_hip_shuffle_split(self.h, sp, kc, pc, len(payload), int(n_rows), int(n_ranks),
-                                               1 if drop_null_keys else 0, counts, C.byref(n_out))
-        if st:
-            _raise(st)
-        n, npay = n_out.value, len(payload)
-        masked = [p[1] is not None for p in payload]
-        if sp == L.MEM_DEVICE:
-            import torch
-            d = "cuda:%d" % self.device
-            new = lambda dt: torch.empty(n, dtype=dt, device=d)
-            cells, knull = new(torch.int64), new(torch.uint8)
-            pays = [new(torch.int64) for _ in range(npay)]
-            pnull = [new(torch.uint8) if m else None for m in masked]
-        else:
-            cells, knull = np.empty(n, np.uint64), np.empty(n, np.uint8)
-            pays = [np.empty(n, np.uint64) for _ in range(npay)]
-            pnull = [np.empty(n, np.uint8) if m else None for m in masked]
+        _check(self.lib.pandrs_hip_shuffle_split(self.h, sp, kc, pc, len(payload), int(n_rows), int(n_ranks),
+                                                 1 if drop_null_keys else 0, counts, C.byref(n_out)))
+        n, npay, dev = n_out.value, len(payload), sp == L.MEM_DEVICE
+        cells, knull = self._empty(n, np.uint64, dev), self._empty(n, np.uint8, dev)
+        pays = [self._empty(n, np.uint64, dev) for _ in range(npay)]
+        pnull = [self._empty(n, np.uint8, dev) if p[1] is not None else None for p in payload]
         pp = (C.c_void_p * max(npay, 1))(*[_ptr(a) for a in pays])
         pn = (C.c_void_p * max(npay, 1))(*[_ptr(a) for a in pnull])
-        st = self.lib.pandrs_hip_shuffle_fetch(self.h, sp, _ptr(cells), _ptr(knull), pp, pn)
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_shuffle_fetch(self.h, sp, _ptr(cells), _ptr(knull), pp, pn))
         return cells, knull, pays, pnull, [int(x) for x in counts]
 
     def key_hash_cells(self, keys, n_rows):
         """One 64-bit hash cell per row of a composite key (the shuffle key of a multi-key groupby)."""
         keep = []
         kc, sp = self._cols(keys, keep)
-        if sp == L.MEM_DEVICE:
-            import torch
-            out = torch.empty(int(n_rows), dtype=torch.int64, device="cuda:%d" % self.device)
-        else:
-            out = np.empty(int(n_rows), np.uint64)
-        st = self.lib.pandrs_hip_key_hash_cells(self.h, sp, kc, len(keys), int(n_rows), _ptr(out))
-        if st:
-            _raise(st)
+        out = self._empty(int(n_rows), np.uint64, sp == L.MEM_DEVICE)
+        _check(self.lib.pandrs_hip_key_hash_cells(self.h, sp, kc, len(keys), int(n_rows), _ptr(out)))
         return out
 
     def bytes_to_bitmap(self, flags):
         """One byte per row (non-zero = set) -> LSB-first bitmap, same kind (numpy / torch) as the input."""
         n = int(flags.shape[0])
-        if _is_torch(flags):
-            import torch
+        dev = _is_torch(flags)
+        if dev:
             self._wait_for_producer()
             flags = flags.contiguous()
-            out = torch.empty((n + 7) // 8, dtype=torch.uint8, device=flags.device)
-            sp = L.MEM_DEVICE
         else:
             flags = np.ascontiguousarray(flags, np.uint8)
-            out = np.empty((n + 7) // 8, np.uint8)
-            sp = L.MEM_HOST
-        st = self.lib.pandrs_hip_bytes_to_bitmap(self.h, sp, _ptr(flags), n, _ptr(out))
-        if st:
-            _raise(st)
+        out = self._empty((n + 7) // 8, np.uint8, dev)
+        _check(self.lib.pandrs_hip_bytes_to_bitmap(self.h, _space(dev), _ptr(flags), n, _ptr(out)))
         return out
 
     # -- mergeable partials (multi-GPU) --------------------------------------------------------------
@@ -409,10 +452,8 @@ class Context:
         kc, sp1 = self._cols(keys, keep)
         vc, _ = self._cols(vals, keep) if vals else ((L.Column * 1)(), sp1)
         ng, ns = C.c_int64(0), C.c_int32(0)
-        st = self.lib.pandrs_hip_groupby_partials(self.h, sp1, kc, len(keys), int(n_rows), vc, len(vals),
-                                                  self._aggs(aggs), len(aggs), C.byref(ng), C.byref(ns))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_groupby_partials(self.h, sp1, kc, len(keys), int(n_rows), vc, len(vals),
+                                                    self._aggs(aggs), len(aggs), C.byref(ng), C.byref(ns)))
         self._last_partials = (ng.value, ns.value, sp1)
         return ng.value, ns.value
 
@@ -423,15 +464,8 @@ class Context:
         g, ns, space = self._last_partials
         dev = space == L.MEM_DEVICE if device is None else device
         counts = (C.c_int64 * n_ranks)()
-        if dev:
-            import torch
-            rec = torch.empty((g, 2 + ns), dtype=torch.int64, device="cuda:%d" % self.device)
-        else:
-            rec = np.empty((g, 2 + ns), np.uint64)
-        st = self.lib.pandrs_hip_partials_split(self.h, L.MEM_DEVICE if dev else L.MEM_HOST, n_ranks,
-                                                _ptr(rec), counts)
-        if st:
-            _raise(st)
+        rec = self._empty((g, 2 + ns), np.uint64, dev)
+        _check(self.lib.pandrs_hip_partials_split(self.h, _space(dev), n_ranks, _ptr(rec), counts))
         return rec, [int(c) for c in counts]
 
     def groupby_merge(self, key_dtype, records, val_dtypes, val_has_nulls, aggs):
@@ -447,12 +481,9 @@ class Context:
         vd = (C.c_int32 * max(nv, 1))(*[int(x) for x in val_dtypes])
         vh = (C.c_uint8 * max(nv, 1))(*[1 if x else 0 for x in val_has_nulls])
         ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_groupby_merge(self.h, L.MEM_DEVICE if dev else L.MEM_HOST, int(key_dtype),
-                                               _ptr(records) if n_rows else None, n_rows,
-                                               vd, nv, vh, self._aggs(aggs), len(aggs), C.byref(ng))
-        if st:
-            _raise(st)
-        self._last = (1, len(aggs), L.MEM_DEVICE if dev else L.MEM_HOST, ng.value)
+        _check(self.lib.pandrs_hip_groupby_merge(self.h, _space(dev), int(key_dtype), _ptr(records) if n_rows else None, n_rows,
+                                                 vd, nv, vh, self._aggs(aggs), len(aggs), C.byref(ng)))
+        self._last = (1, len(aggs), _space(dev), ng.value)
         return ng.value
 
     # -- join --------------------------------------------------------------------------------------------
@@ -464,41 +495,24 @@ class Context:
         if sp1 != sp2:
             raise ValueError("both key columns must live in the same memory space")
         n = C.c_int64(0)
-        st = self.lib.pandrs_hip_join_indices(self.h, sp1, lc, int(n_left), rc, int(n_right), int(how), C.byref(n))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_join_indices(self.h, sp1, lc, int(n_left), rc, int(n_right), int(how), C.byref(n)))
         return n.value, sp1
 
     def join_indices(self, lkey, n_left, rkey, n_right, how):
         n, sp1 = self.join_indices_compute(lkey, n_left, rkey, n_right, how)
-        if sp1 == L.MEM_DEVICE:
-            import torch
-            d = "cuda:%d" % self.device
-            li = torch.empty(n, dtype=torch.int64, device=d)
-            ri = torch.empty(n, dtype=torch.int64, device=d)
-        else:
-            li, ri = np.empty(n, np.int64), np.empty(n, np.int64)
-        st = self.lib.pandrs_hip_join_fetch(self.h, sp1, _ptr(li), _ptr(ri))
-        if st:
-            _raise(st)
+        li, ri = self._empty(n, np.int64, sp1 == L.MEM_DEVICE), self._empty(n, np.int64, sp1 == L.MEM_DEVICE)
+        _check(self.lib.pandrs_hip_join_fetch(self.h, sp1, _ptr(li), _ptr(ri)))
         return li, ri
 
     def gather(self, src, mask, idx, fill, dtype):
         """Device tensors only.  -> torch tensor (uint8 per row for BOOLBITS sources)."""
-        import torch
         self._wait_for_producer()        # src / mask / idx may still be being written on torch's current stream
         n = idx.numel()
-        d = idx.device
-        fn, out = {
-            L.I64: (self.lib.pandrs_hip_gather_i64, torch.empty(n, dtype=torch.int64, device=d)),
-            L.F64: (self.lib.pandrs_hip_gather_f64, torch.empty(n, dtype=torch.float64, device=d)),
-            L.U32CODE: (self.lib.pandrs_hip_gather_u32, torch.empty(n, dtype=torch.int32, device=d)),
-            L.BOOLBITS: (self.lib.pandrs_hip_gather_bool, torch.empty(n, dtype=torch.uint8, device=d)),
-        }[dtype]
+        fn = {L.I64: self.lib.pandrs_hip_gather_i64, L.F64: self.lib.pandrs_hip_gather_f64,
+              L.U32CODE: self.lib.pandrs_hip_gather_u32, L.BOOLBITS: self.lib.pandrs_hip_gather_bool}[dtype]
+        out = self._empty(n, _NP_OF[dtype], True)
         fill = float(fill) if dtype == L.F64 else int(fill)
-        st = fn(self.h, L.MEM_DEVICE, _ptr(src), _ptr(mask), _ptr(idx), n, fill, _ptr(out))
-        if st:
-            _raise(st)
+        _check(fn(self.h, L.MEM_DEVICE, _ptr(src), _ptr(mask), _ptr(idx), n, fill, _ptr(out)))
         return out
 
     def join_gather(self, col, n_src, n_out, side, fill=0, key_right=None, n_right=0):
@@ -506,44 +520,37 @@ class Context:
         pandrs_hip_join_gather (side 0 = the pairs' left rows, 1 = their right rows), or — key_right given — pandrs_hip_join_gather_key
         (the left key's value, else the right key's: join.rs:364-470).  `col` is a (data, mask, dtype) triple on the host or the
         device, or a ResidentColumn; -> numpy array of n_out elements (uint8 per row for BOOLBITS sources)."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         dtype = tuple(col)[2]
         out = np.empty(int(n_out), {L.I64: np.int64, L.F64: np.float64, L.U32CODE: np.uint32, L.BOOLBITS: np.uint8}[dtype])
-        fill_bits = int(np.float64(fill).view(np.uint64)) if dtype == L.F64 else int(fill) & 0xFFFFFFFFFFFFFFFF
         if key_right is None:
-            st = self.lib.pandrs_hip_join_gather(self.h, sp, cc, int(n_src), int(side), fill_bits, L.MEM_HOST, _ptr(out))
+            _check(self.lib.pandrs_hip_join_gather(self.h, sp, cc, int(n_src), int(side), _fill_bits(fill, dtype), L.MEM_HOST, _ptr(out)))
         else:
             kc, sp2 = self._cols([tuple(key_right)], keep)
             if sp2 != sp:
                 raise ValueError("both key columns must live in one memory space")
-            st = self.lib.pandrs_hip_join_gather_key(self.h, sp, cc, int(n_src), kc, int(n_right), fill_bits, L.MEM_HOST, _ptr(out))
-        if st:
-            _raise(st)
+            _check(self.lib.pandrs_hip_join_gather_key(self.h, sp, cc, int(n_src), kc, int(n_right), _fill_bits(fill, dtype),
+                                                       L.MEM_HOST, _ptr(out)))
         return out
 
-    def join_groupby_sum(self, lkey, lval, n_left, rkey, rgroup, n_right):
+    def _join_groupby_sum(self, call, head, lkey, lval, n_left, rkey, rgroup, n_right):
+        """call(*head, space, left key, left value, n_left, right key, right group, n_right, &n_groups), then the fetch."""
         keep = []
-        a, sp = self._cols([lkey], keep)
-        b, _ = self._cols([lval], keep)
-        c, _ = self._cols([rkey], keep)
-        d, _ = self._cols([rgroup], keep)
+        (a, sp), (b, _), (c, _), (d, _) = [self._cols([x], keep) for x in (lkey, lval, rkey, rgroup)]
         ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_join_groupby_sum(self.h, sp, a, b, int(n_left), c, d, int(n_right), C.byref(ng))
-        if st:
-            _raise(st)
+        _check(call(*head, sp, a, b, int(n_left), c, d, int(n_right), C.byref(ng)))
         self._last = (1, 1, sp, ng.value)
         return self.groupby_fetch()
+
+    def join_groupby_sum(self, lkey, lval, n_left, rkey, rgroup, n_right):
+        return self._join_groupby_sum(self.lib.pandrs_hip_join_groupby_sum, (self.h,), lkey, lval, n_left, rkey, rgroup, n_right)
 
     def column_std(self, col, n, population=True):
         """parallel_std_f64_value / parallel_var (jit/parallel.rs:222-250): sqrt(max(sum_sq / n - mean^2, 0)),
         n <= 1 => 0.0.  -> (std, variance)."""
-        keep = []
-        cc, sp = self._cols([col], keep)
+        cc, sp, keep = self._col(col)
         s, q, cnt = C.c_double(0), C.c_double(0), C.c_int64(0)
-        st = self.lib.pandrs_hip_reduce_moments(self.h, sp, cc, int(n), C.byref(s), C.byref(q), C.byref(cnt))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_reduce_moments(self.h, sp, cc, int(n), C.byref(s), C.byref(q), C.byref(cnt)))
         m = cnt.value
         if m <= 1:
             return 0.0, 0.0
@@ -558,16 +565,12 @@ class Context:
     def comm_unique_id():
         """128 bytes from rank 0 (ncclGetUniqueId); the host hands them to every rank over any channel."""
         buf = C.create_string_buffer(128)
-        st = L.load().pandrs_hip_comm_unique_id(buf)
-        if st:
-            _raise(st)
+        _check(L.load().pandrs_hip_comm_unique_id(buf))
         return buf.raw
 
     def comm_init(self, unique_id, rank, world):
         h = C.c_void_p()
-        st = self.lib.pandrs_hip_comm_init(self.h, C.c_char_p(bytes(unique_id)), int(rank), int(world), C.byref(h))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_comm_init(self.h, C.c_char_p(bytes(unique_id)), int(rank), int(world), C.byref(h)))
         self.comm = h
         self.comm_world = world
         return h
@@ -614,9 +617,7 @@ class Context:
 
         t = L.Transport(None, L.ALL_GATHER_FN(_ag), L.ALL_REDUCE_MAX_FN(_ar), L.ALL_TO_ALL_V_FN(_a2a))
         h = C.c_void_p()
-        st = self.lib.pandrs_hip_comm_adopt_transport(C.byref(t), int(rank), int(world), C.byref(h))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_comm_adopt_transport(C.byref(t), int(rank), int(world), C.byref(h)))
         self._transport = t            # the callbacks must outlive the communicator
         self.comm = h
         self.comm_world = world
@@ -639,9 +640,7 @@ class Context:
     def poison_workspace(byte):
         """Testing knob (process-wide): fill every workspace block with `byte` (0 ... 255) before a call uses it; None = off."""
         value = 0 if byte is None else (int(byte) & 0xFF) or 0x100
-        st = L.load().pandrs_hip_ctx_set_option(None, b"poison_workspace", value)
-        if st:
-            _raise(st)
+        _check(L.load().pandrs_hip_ctx_set_option(None, b"poison_workspace", value))
 
     def comm_destroy(self):
         if getattr(self, "comm", None):
@@ -654,45 +653,28 @@ class Context:
         kc, sp1 = self._cols(keys, keep)
         vc, _ = self._cols(vals, keep) if vals else ((L.Column * 1)(), sp1)
         ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_dist_groupby_agg(self.h, self.comm, sp1, kc, len(keys), int(n_rows), vc, len(vals),
-                                                  self._aggs(aggs), len(aggs), C.byref(ng))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_dist_groupby_agg(self.h, self.comm, sp1, kc, len(keys), int(n_rows), vc, len(vals),
+                                                    self._aggs(aggs), len(aggs), C.byref(ng)))
         general = len(keys) > 1 or any(int(op) > L.COUNT for _, op in aggs)
         self._last = (len(keys), len(aggs), L.MEM_DEVICE if general else sp1, ng.value)     # the row shuffle leaves its result on the device
         return ng.value
 
     def dist_join_groupby_sum(self, lkey, lval, n_left, rkey, rgroup, n_right):
-        keep = []
-        a, sp = self._cols([lkey], keep)
-        b, _ = self._cols([lval], keep)
-        c, _ = self._cols([rkey], keep)
-        d, _ = self._cols([rgroup], keep)
-        ng = C.c_int64(0)
-        st = self.lib.pandrs_hip_dist_join_groupby_sum(self.h, self.comm, sp, a, b, int(n_left), c, d, int(n_right), C.byref(ng))
-        if st:
-            _raise(st)
-        self._last = (1, 1, sp, ng.value)
-        return self.groupby_fetch()
+        return self._join_groupby_sum(self.lib.pandrs_hip_dist_join_groupby_sum, (self.h, self.comm), lkey, lval, n_left, rkey, rgroup,
+                                      n_right)
 
     def column_stats(self, col, n):
         """pandrs_hip_reduce_stats: one pass, everything K1's reference functions need.  -> dict."""
-        keep = []
-        cc, sp = self._cols([col], keep)
+        cc, sp, keep = self._col(col)
         out = L.ColumnStats()
-        st = self.lib.pandrs_hip_reduce_stats(self.h, sp, cc, int(n), C.byref(out))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_reduce_stats(self.h, sp, cc, int(n), C.byref(out)))
         return {name: getattr(out, name) for name, _ in L.ColumnStats._fields_}
 
     def reduce_column(self, col, n):
-        keep = []
-        cc, sp = self._cols([col], keep)
+        cc, sp, keep = self._col(col)
         out = (C.c_double * 4)()
         cnt = C.c_int64(0)
-        st = self.lib.pandrs_hip_reduce_column(self.h, sp, cc, int(n), out, C.byref(cnt))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_reduce_column(self.h, sp, cc, int(n), out, C.byref(cnt)))
         return np.array(list(out)), cnt.value
 
     # -- sort ----------------------------------------------------------------------------------------------
@@ -703,29 +685,16 @@ class Context:
         (host, device or ResidentColumn), `ascending` one flag per key (None = all ascending), `code_rank` the string
         pool's rank table (rank[code] = position of the code's string in byte-wise order), needed when a key is a
         string column.  -> int64 torch tensor of n_rows row indices on this context's device."""
-        import torch
         keep = []
         kc, sp = self._cols(keys, keep)
         nk = len(keys)
         asc = None
         if ascending is not None:
             asc = (C.c_int32 * max(nk, 1))(*[1 if a else 0 for a in ascending])
-        rank, n_codes = None, 0
-        if code_rank is not None:
-            if sp == L.MEM_DEVICE:
-                rank = code_rank if _is_torch(code_rank) else torch.from_numpy(
-                    np.ascontiguousarray(code_rank, dtype=np.uint32).view(np.int32)).to("cuda:%d" % self.device)
-                if _is_torch(code_rank):
-                    self._wait_for_producer()
-            else:
-                rank = np.ascontiguousarray(code_rank.cpu().numpy() if _is_torch(code_rank) else code_rank).view(np.uint32)
-            keep.append(rank)
-            n_codes = int(rank.numel() if _is_torch(rank) else rank.shape[0])
-        out = torch.empty(int(n_rows), dtype=torch.int64, device="cuda:%d" % self.device)
-        st = self.lib.pandrs_hip_sort_indices(self.h, sp, kc, nk, asc, _ptr(rank), n_codes, int(n_rows), L.MEM_DEVICE,
-                                              _ptr(out) if n_rows else None)
-        if st:
-            _raise(st)
+        rank, n_codes = self._code_rank(code_rank, sp, keep)
+        out = self._empty(int(n_rows), np.int64, True)
+        _check(self.lib.pandrs_hip_sort_indices(self.h, sp, kc, nk, asc, _ptr(rank), n_codes, int(n_rows), L.MEM_DEVICE,
+                                                _ptr(out) if n_rows else None))
         return out
 
     # -- filter (stream compaction) ---------------------------------------------------------------------------
@@ -735,14 +704,10 @@ class Context:
         (bits, null_mask, dtype) triple (host, device or ResidentColumn).  The context keeps the selection for
         filter_gather until the next filter_indices.  -> (int64 torch tensor of the selected rows on this context's
         device, or None when indices=False, selected row count)."""
-        import torch
-        keep = []
-        cc, sp = self._cols([tuple(cond)], keep)
-        out = torch.empty(max(int(n_rows), 1), dtype=torch.int64, device="cuda:%d" % self.device) if indices else None
+        cc, sp, keep = self._col(cond)
+        out = self._empty(max(int(n_rows), 1), np.int64, True) if indices else None
         cnt = C.c_int64(0)
-        st = self.lib.pandrs_hip_filter_indices(self.h, sp, cc, int(n_rows), L.MEM_DEVICE, _ptr(out), C.byref(cnt))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_filter_indices(self.h, sp, cc, int(n_rows), L.MEM_DEVICE, _ptr(out), C.byref(cnt)))
         return (out[:cnt.value] if indices else None), cnt.value
 
     def filter_gather(self, col, n_src, n_out, fill=0, out_device=False):
@@ -751,20 +716,12 @@ class Context:
         host or the device, or a ResidentColumn; n_out = the selection's count.  -> numpy array of n_out elements
         (uint8 per row for BOOLBITS sources), or with out_device a torch tensor on this context's device (int32 for
         U32CODE)."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         dtype = tuple(col)[2]
-        if out_device:
-            import torch
-            out = torch.empty(int(n_out), dtype={L.I64: torch.int64, L.F64: torch.float64, L.U32CODE: torch.int32,
-                                                 L.BOOLBITS: torch.uint8}.get(dtype, torch.int64), device="cuda:%d" % self.device)
-        else:
-            out = np.empty(int(n_out), {L.F64: np.float64, L.U32CODE: np.uint32, L.BOOLBITS: np.uint8}.get(dtype, np.int64))
-        fill_bits = int(np.float64(fill).view(np.uint64)) if dtype == L.F64 else int(fill) & 0xFFFFFFFFFFFFFFFF
-        st = self.lib.pandrs_hip_filter_gather(self.h, sp, cc, int(n_src), fill_bits, L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                               _ptr(out) if int(n_out) else None)
-        if st:
-            _raise(st)
+        np_dtype = {L.F64: np.float64, L.U32CODE: np.uint32, L.BOOLBITS: np.uint8}.get(dtype, np.int64)
+        out, out_device = self._out_buffer(int(n_out), np_dtype, sp, None, bool(out_device), "n_out")
+        _check(self.lib.pandrs_hip_filter_gather(self.h, sp, cc, int(n_src), _fill_bits(fill, dtype), _space(out_device),
+                                                 _ptr(out) if int(n_out) else None))
         return out
 
     # -- window statistics (rolling / expanding / EWM) ----------------------------------------------------------
@@ -775,23 +732,13 @@ class Context:
         window), center and ddof as the rolling spec, alpha resolved by the caller (EWM).  -> n_rows float64 values,
         NaN for None: a torch tensor on this context's device for device / resident columns (or out_device=True),
         else a numpy array."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n = int(n_rows)
         spec = L.WindowSpec(kind=int(kind), op=int(op), window=int(window), min_periods=int(min_periods),
                             center=1 if center else 0, reserved=0, ddof=int(ddof), alpha=float(alpha))
-        if out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
-        else:
-            out = np.empty(n, np.float64)
-        st = self.lib.pandrs_hip_window(self.h, sp, cc, n, C.byref(spec), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                        _ptr(out) if n else None)
-        if st:
-            _raise(st)
-        return out[:n] if out_device else out
+        out, out_device = self._out_buffer(n, np.float64, sp, None, out_device, "n_rows")
+        _check(self.lib.pandrs_hip_window(self.h, sp, cc, n, C.byref(spec), _space(out_device), _ptr(out) if n else None))
+        return out
 
     def window_quantile(self, col, n_rows, kind, *, median=True, q=0.5, window=0, min_periods=-1, center=False, nan_missing=False,
                         out_device=None):
@@ -801,23 +748,13 @@ class Context:
         window, min_periods (< 0 = window) and center as in window(); nan_missing=True also skips NaN cells
         (window_ops.rs:221).  A window with fewer than min_periods values, or none, gives NaN, as does (without
         nan_missing) one that holds a NaN value.  Same return conventions as window()."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n = int(n_rows)
         spec = L.WindowQuantileSpec(kind=int(kind), median=1 if median else 0, window=int(window), min_periods=int(min_periods),
                                     center=1 if center else 0, nan_missing=1 if nan_missing else 0, q=float(q))
-        if out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
-        else:
-            out = np.empty(n, np.float64)
-        st = self.lib.pandrs_hip_window_quantile(self.h, sp, cc, n, C.byref(spec), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                                 _ptr(out) if n else None)
-        if st:
-            _raise(st)
-        return out[:n] if out_device else out
+        out, out_device = self._out_buffer(n, np.float64, sp, None, out_device, "n_rows")
+        _check(self.lib.pandrs_hip_window_quantile(self.h, sp, cc, n, C.byref(spec), _space(out_device), _ptr(out) if n else None))
+        return out
 
     # -- describe / exact percentiles (radix select) -------------------------------------------------------------
     def describe(self, col, n_rows):
@@ -825,27 +762,21 @@ class Context:
         OptimizedDataFrame::describe, split_dataframe/stats.rs:50-151 over stats/descriptive.rs:91-200).  `col` is a
         (data, mask, dtype) triple on the host or the device, or a ResidentColumn.  -> dict with the fields of
         pandrs_hip_describe_stats (count, mean, std, min, q1, median, q3, max); count 0 gives NaN everywhere."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         out = L.DescribeStats()
-        st = self.lib.pandrs_hip_describe(self.h, sp, cc, int(n_rows), C.byref(out))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_describe(self.h, sp, cc, int(n_rows), C.byref(out)))
         return {name: getattr(out, name) for name, _ in L.DescribeStats._fields_}
 
     def quantiles(self, col, n_rows, percentiles):
         """percentile(sorted non-null values, p) (stats/descriptive.rs:169-200) for 1 to 16 values of p in [0, 100], in any
         order, on the device (pandrs_hip_quantiles).  `col` as in describe.  -> (float64 numpy array, one value per p,
         NaN when the column has no non-null cell; the non-null count)."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         ps = np.ascontiguousarray(percentiles, dtype=np.float64).reshape(-1)
         out = np.empty(max(ps.shape[0], 1), np.float64)
         cnt = C.c_int64(0)
-        st = self.lib.pandrs_hip_quantiles(self.h, sp, cc, int(n_rows), ps.ctypes.data_as(C.POINTER(C.c_double)), int(ps.shape[0]),
-                                           out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_quantiles(self.h, sp, cc, int(n_rows), ps.ctypes.data_as(C.POINTER(C.c_double)), int(ps.shape[0]),
+                                             out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
         return out[:ps.shape[0]], cnt.value
 
     # -- rank (radix sort, tie-run boundaries, scatter) ------------------------------------------------------------
@@ -856,32 +787,11 @@ class Context:
         cells get NaN and take no rank.  `out`: a float64 numpy array or torch CUDA tensor of at least n_rows elements to
         write into.  -> n_rows float64 ranks: `out` when given; else a torch tensor on this context's device for device /
         resident columns (or out_device=True), else a numpy array."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n = int(n_rows)
-        if out is not None:
-            out_device = _is_torch(out)
-            if out_device:
-                import torch
-                ok = out.dtype == torch.float64 and out.is_contiguous() and out.is_cuda and out.numel() >= n
-            else:
-                ok = isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.size >= n
-            if not ok:
-                raise ValueError("out must be a contiguous float64 numpy array or CUDA tensor of at least n_rows elements")
-            if out_device:
-                self._wait_for_producer()
-        else:
-            if out_device is None:
-                out_device = sp == L.MEM_DEVICE
-            if out_device:
-                import torch
-                out = torch.empty(max(n, 1), dtype=torch.float64, device="cuda:%d" % self.device)
-            else:
-                out = np.empty(n, np.float64)
-        st = self.lib.pandrs_hip_rank(self.h, sp, cc, n, int(method), L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if n else None)
-        if st:
-            _raise(st)
-        return out[:n]
+        out, out_device = self._out_buffer(n, np.float64, sp, out, out_device, "n_rows")
+        _check(self.lib.pandrs_hip_rank(self.h, sp, cc, n, int(method), _space(out_device), _ptr(out) if n else None))
+        return out
 
     # -- fill (valid bits, a carry across tiles, a nearby gather) ------------------------------------------------------
     def fill(self, col, n_rows, method, value=None, out=None, out_mask=None, out_device=None):
@@ -895,83 +805,26 @@ class Context:
         is the uint8 null bitmap of the rows still missing, None when n_missing == 0.  Both are `out` / `out_mask` when
         given; else torch tensors on this context's device for device / resident columns (or out_device=True), else
         numpy arrays."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n, method = int(n_rows), int(method)
         is_i64 = cc[0].dtype == L.I64
-        out_i64 = is_i64 and method != L.FILL_LINEAR
         fill_bits = 0
         if method == L.FILL_VALUE:
             if is_i64:
                 if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not -(1 << 63) <= int(value) < (1 << 63):
                     raise ValueError("an I64 column is filled with an int that fits int64, got %r" % (value,))
-                fill_bits = int(value) & 0xFFFFFFFFFFFFFFFF
-            else:
-                if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
-                    raise ValueError("an F64 column is filled with a float, got %r" % (value,))
-                fill_bits = int(np.float64(value).view(np.uint64))
+            elif isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+                raise ValueError("an F64 column is filled with a float, got %r" % (value,))
+            fill_bits = _fill_bits(value, L.I64 if is_i64 else L.F64)
         elif value is not None:
             raise ValueError("value goes with FILL_VALUE only")
-        nbytes = (n + 7) // 8
-        given = [b for b in (out, out_mask) if b is not None]
-        if given:
-            if len({_is_torch(b) for b in given}) != 1:
-                raise ValueError("out and out_mask must both be numpy arrays or both CUDA tensors")
-            out_device = _is_torch(given[0])
-        elif out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            want, want_mask = (torch.int64 if out_i64 else torch.float64), torch.uint8
-            good = lambda b, dt, k: b.dtype == dt and b.is_contiguous() and b.is_cuda and b.numel() >= k  # noqa: E731
-            make = lambda dt, k: torch.empty(max(k, 1), dtype=dt, device="cuda:%d" % self.device)        # noqa: E731
-        else:
-            want, want_mask = (np.int64 if out_i64 else np.float64), np.uint8
-            good = lambda b, dt, k: isinstance(b, np.ndarray) and b.dtype == dt and b.flags.c_contiguous and b.size >= k  # noqa: E731
-            make = lambda dt, k: np.empty(k, dt)                                                                       # noqa: E731
-        if out is not None and not good(out, want, n):
-            raise ValueError("out must be a contiguous %s numpy array or CUDA tensor of at least n_rows elements" % ("int64" if out_i64 else "float64"))
-        if out_mask is not None and not good(out_mask, want_mask, nbytes):
-            raise ValueError("out_mask must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
-        if given and out_device:
-            self._wait_for_producer()
-        out = make(want, n) if out is None else out
-        out_mask = make(want_mask, nbytes) if out_mask is None else out_mask
+        out, out_mask, out_device = self._cell_outs(n, sp, is_i64 and method != L.FILL_LINEAR, out, out_mask, out_device)
         missing = C.c_int64(0)
-        st = self.lib.pandrs_hip_fill(self.h, sp, cc, n, method, C.c_uint64(fill_bits), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                      _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(missing))
-        if st:
-            _raise(st)
-        return out[:n], (out_mask[:nbytes] if missing.value else None), missing.value
+        _check(self.lib.pandrs_hip_fill(self.h, sp, cc, n, method, C.c_uint64(fill_bits), _space(out_device),
+                                        _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(missing)))
+        return out, (out_mask if missing.value else None), missing.value
 
     # -- cumulative folds and lags (reduce then apply over spans; one stream) -----------------------------------------
-    def _cell_outs(self, n, sp, want_i64, out, out_mask, out_device):
-        """The (out, out_mask, out_device) a call with one 8-byte cell per row and a null bitmap writes into."""
-        nbytes = (n + 7) // 8
-        given = [b for b in (out, out_mask) if b is not None]
-        if given:
-            if len({_is_torch(b) for b in given}) != 1:
-                raise ValueError("out and out_mask must both be numpy arrays or both CUDA tensors")
-            out_device = _is_torch(given[0])
-        elif out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            want, want_mask = (torch.int64 if want_i64 else torch.float64), torch.uint8
-            good = lambda b, dt, k: b.dtype == dt and b.is_contiguous() and b.is_cuda and b.numel() >= k  # noqa: E731
-            make = lambda dt, k: torch.empty(max(k, 1), dtype=dt, device="cuda:%d" % self.device)        # noqa: E731
-        else:
-            want, want_mask = (np.int64 if want_i64 else np.float64), np.uint8
-            good = lambda b, dt, k: isinstance(b, np.ndarray) and b.dtype == dt and b.flags.c_contiguous and b.size >= k  # noqa: E731
-            make = lambda dt, k: np.empty(k, dt)                                                                       # noqa: E731
-        if out is not None and not good(out, want, n):
-            raise ValueError("out must be a contiguous %s numpy array or CUDA tensor of at least n_rows elements" % ("int64" if want_i64 else "float64"))
-        if out_mask is not None and not good(out_mask, want_mask, nbytes):
-            raise ValueError("out_mask must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
-        if given and out_device:
-            self._wait_for_producer()
-        return (make(want, n) if out is None else out), (make(want_mask, nbytes) if out_mask is None else out_mask), out_device
-
     def cumulative(self, col, n_rows, op, out=None, out_mask=None, out_device=None):
         """The running fold of one I64 / F64 column on the device (pandrs_hip_cumulative; PandasCompatExt::cumsum / cumprod /
         cummax / cummin / cumcount, src/dataframe/pandas_compat/functions.rs:280-327, :2081-2094): row i covers rows 0 .. i.
@@ -981,16 +834,13 @@ class Context:
         cells / ceil(n_rows / 8) uint8 to write into.  -> (values, mask, n_null): mask is the uint8 null bitmap of the
         result, None when n_null == 0.  Both are `out` / `out_mask` when given; else torch tensors on this context's device
         for device / resident columns (or out_device=True), else numpy arrays."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n, op = int(n_rows), int(op)
         out, out_mask, out_device = self._cell_outs(n, sp, op == L.CUM_COUNT, out, out_mask, out_device)
         nulls = C.c_int64(0)
-        st = self.lib.pandrs_hip_cumulative(self.h, sp, cc, n, op, L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                            _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
-        if st:
-            _raise(st)
-        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+        _check(self.lib.pandrs_hip_cumulative(self.h, sp, cc, n, op, _space(out_device),
+                                              _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls)))
+        return out, (out_mask if nulls.value else None), nulls.value
 
     def lag(self, col, n_rows, op, periods, out=None, out_mask=None, out_device=None):
         """One I64 / F64 column against itself `periods` rows earlier (pandrs_hip_lag; PandasCompatExt::shift / diff /
@@ -998,18 +848,15 @@ class Context:
         with a null one, is NaN with its bit set), L.LAG_DIFF or L.LAG_PCT_CHANGE (periods >= 0; rows i < periods are NaN
         values with bit 0; a null operand is NaN with its bit set).  Buffers and the result as Context.cumulative; values are
         float64."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n, op, periods = int(n_rows), int(op), int(periods)
         if not -(1 << 63) <= periods < (1 << 63):
             raise ValueError("periods must fit int64, got %d" % periods)
         out, out_mask, out_device = self._cell_outs(n, sp, False, out, out_mask, out_device)
         nulls = C.c_int64(0)
-        st = self.lib.pandrs_hip_lag(self.h, sp, cc, n, op, C.c_int64(periods), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                     _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
-        if st:
-            _raise(st)
-        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+        _check(self.lib.pandrs_hip_lag(self.h, sp, cc, n, op, C.c_int64(periods), _space(out_device),
+                                       _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls)))
+        return out, (out_mask if nulls.value else None), nulls.value
 
     def grouped(self, col, n_rows, op, periods=0, out=None, out_mask=None, out_device=None):
         """Context.cumulative / Context.lag within the groups this context retains from its last groupby_indices
@@ -1017,21 +864,18 @@ class Context:
         rows.  op is L.GROUPED_CUM_SUM / CUM_MAX / CUM_MIN / CUM_COUNT / ROW_NUMBER / SHIFT / DIFF / PCT_CHANGE; `periods` is
         read by the last three.  `col` as Context.cumulative; None for ROW_NUMBER, which reads no column.  n_rows must be the
         grouping's.  Buffers and the result as Context.cumulative; CUM_COUNT and ROW_NUMBER give int64."""
-        keep = []
         n, op, periods = int(n_rows), int(op), int(periods)
         if not -(1 << 63) <= periods < (1 << 63):
             raise ValueError("periods must fit int64, got %d" % periods)
         if col is None:
-            cc, sp = None, (L.MEM_DEVICE if out_device or _is_torch(out) else L.MEM_HOST)
+            cc, sp = None, _space(out_device or _is_torch(out))
         else:
-            cc, sp = self._cols([tuple(col)], keep)
+            cc, sp, keep = self._col(col)
         out, out_mask, out_device = self._cell_outs(n, sp, op in (L.GROUPED_CUM_COUNT, L.GROUPED_ROW_NUMBER), out, out_mask, out_device)
         nulls = C.c_int64(0)
-        st = self.lib.pandrs_hip_grouped(self.h, sp, cc, n, op, C.c_int64(periods), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                         _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls))
-        if st:
-            _raise(st)
-        return out[:n], (out_mask[:(n + 7) // 8] if nulls.value else None), nulls.value
+        _check(self.lib.pandrs_hip_grouped(self.h, sp, cc, n, op, C.c_int64(periods), _space(out_device),
+                                           _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(nulls)))
+        return out, (out_mask if nulls.value else None), nulls.value
 
     # -- top-k (radix select, compaction, a sort of fewer than k rows) ---------------------------------------------------
     def topk(self, col, n_rows, k, largest=True, out=None, out_device=None):
@@ -1042,76 +886,26 @@ class Context:
         array or torch CUDA tensor of at least min(k, n_rows) elements to write into.  -> (rows, n_numbers): the int64 row
         indices (`out` when given; else a torch tensor on this context's device for device / resident columns or
         out_device=True, else a numpy array) and how many of them hold a number (they come first)."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n, k = int(n_rows), int(k)
         kk = max(0, min(k, n))
-        if out is not None:
-            out_device = _is_torch(out)
-            if out_device:
-                import torch
-                ok = out.dtype == torch.int64 and out.is_contiguous() and out.is_cuda and out.numel() >= kk
-            else:
-                ok = isinstance(out, np.ndarray) and out.dtype == np.int64 and out.flags.c_contiguous and out.size >= kk
-            if not ok:
-                raise ValueError("out must be a contiguous int64 numpy array or CUDA tensor of at least min(k, n_rows) elements")
-            if out_device:
-                self._wait_for_producer()
-        else:
-            if out_device is None:
-                out_device = sp == L.MEM_DEVICE
-            if out_device:
-                import torch
-                out = torch.empty(max(kk, 1), dtype=torch.int64, device="cuda:%d" % self.device)
-            else:
-                out = np.empty(kk, np.int64)
+        out, out_device = self._out_buffer(kk, np.int64, sp, out, out_device, "min(k, n_rows)")
         cnt, num = C.c_int64(0), C.c_int64(0)
-        st = self.lib.pandrs_hip_topk(self.h, sp, cc, n, k, L.TOPK_LARGEST if largest else L.TOPK_SMALLEST,
-                                      L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if kk else None, C.byref(cnt), C.byref(num))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_topk(self.h, sp, cc, n, k, L.TOPK_LARGEST if largest else L.TOPK_SMALLEST,
+                                        _space(out_device), _ptr(out) if kk else None, C.byref(cnt), C.byref(num)))
         return out[:cnt.value], num.value
 
     def arg_extreme(self, col, n_rows):
         """idxmin and idxmax of one I64 / F64 column in one pass on the device (pandrs_hip_arg_extreme; functions.rs:175-192):
         -> (the FIRST row that holds the minimum, the LAST row that holds the maximum), NaN and null cells skipped; None when
         the column holds no number.  `col` as in topk."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         rows = (C.c_int64 * 2)(-1, -1)
         found = C.c_int32(0)
-        st = self.lib.pandrs_hip_arg_extreme(self.h, sp, cc, int(n_rows), rows, C.byref(found))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_arg_extreme(self.h, sp, cc, int(n_rows), rows, C.byref(found)))
         return (int(rows[0]), int(rows[1])) if found.value else None
 
     # -- row masks (a compare stream, a set probe) ------------------------------------------------------------------------
-    def _mask_out(self, n, sp, out, out_device, count_only):
-        """The out_bits buffer of predicate / isin: -> (buffer or None, lives on the device)."""
-        nbytes = (n + 7) // 8
-        if count_only:
-            if out is not None:
-                raise ValueError("count_only takes no out")
-            return None, False
-        if out is not None:
-            out_device = _is_torch(out)
-            if out_device:
-                import torch
-                ok = out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda and out.numel() >= nbytes
-            else:
-                ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= nbytes
-            if not ok:
-                raise ValueError("out must be a contiguous uint8 numpy array or CUDA tensor of at least ceil(n_rows / 8) elements")
-            if out_device:
-                self._wait_for_producer()
-            return out, out_device
-        if out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            return torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda:%d" % self.device), True
-        return np.empty(nbytes, np.uint8), False
-
     def predicate(self, col, n_rows, op, a=0.0, b=0.0, out=None, out_device=None, count_only=False):
         """One row mask of one I64 / F64 column on the device (pandrs_hip_predicate; PandasCompatExt::gt / ge / lt / le /
         eq_value / ne_value / between / is_between / isna / notna / is_finite / is_infinite,
@@ -1122,16 +916,13 @@ class Context:
         is selected - the data of a BOOLBITS column, which filter_indices takes as (bits, None, L.BOOLBITS) - and the number
         of set bits.  bits is `out` when given; else a torch tensor on this context's device for device / resident columns
         (or out_device=True), else a numpy array; None with count_only."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n = int(n_rows)
         out, out_device = self._mask_out(n, sp, out, out_device, count_only)
         cnt = C.c_int64(0)
-        st = self.lib.pandrs_hip_predicate(self.h, sp, cc, n, int(op), float(a), float(b), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                           _ptr(out) if n else None, C.byref(cnt))
-        if st:
-            _raise(st)
-        return (None if out is None else out[:(n + 7) // 8]), cnt.value
+        _check(self.lib.pandrs_hip_predicate(self.h, sp, cc, n, int(op), float(a), float(b), _space(out_device),
+                                             _ptr(out) if n else None, C.byref(cnt)))
+        return out, cnt.value
 
     # -- bins (the edge list from the radix select, one stream for the codes and the counts) ------------------------------
     def bin_edges(self, col, n_rows, kind, k):
@@ -1140,41 +931,13 @@ class Context:
         :2392-2397), bit for bit.  `col` is a (data, mask, dtype) triple on the host or the device, or a ResidentColumn.
         -> (k + 1 float64 edges as a numpy array, the number of cells that are neither null nor NaN); no such cell: every
         edge is NaN.  qcut adds 0.001 to the last edge when it looks rows up: that is the caller's step."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         k = int(k)
         out = np.empty(max(k, 0) + 1, np.float64)
         valid = C.c_int64(0)
-        st = self.lib.pandrs_hip_bin_edges(self.h, sp, cc, int(n_rows), int(kind), k, out.ctypes.data_as(C.POINTER(C.c_double)),
-                                           C.byref(valid))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_bin_edges(self.h, sp, cc, int(n_rows), int(kind), k, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                             C.byref(valid)))
         return out, valid.value
-
-    def _codes_out(self, n, sp, out, out_device, want_codes):
-        """The out_codes buffer of bin, as _mask_out: -> (buffer or None, lives on the device)."""
-        if not want_codes:
-            if out is not None:
-                raise ValueError("want_codes=False takes no out")
-            return None, False
-        if out is not None:
-            out_device = _is_torch(out)
-            if out_device:
-                import torch
-                ok = out.dtype == torch.int32 and out.is_contiguous() and out.is_cuda and out.numel() >= n
-            else:
-                ok = isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.size >= n
-            if not ok:
-                raise ValueError("out must be a contiguous int32 numpy array or CUDA tensor of at least n_rows elements")
-            if out_device:
-                self._wait_for_producer()
-            return out, out_device
-        if out_device is None:
-            out_device = sp == L.MEM_DEVICE
-        if out_device:
-            import torch
-            return torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device), True
-        return np.empty(n, np.int32), False
 
     def bin(self, col, n_rows, edges, out_device=None, want_counts=True, out=None, want_codes=True):
         """The bin of every row of one I64 / F64 column on the device (pandrs_hip_bin): code i where edges[i] <= v <
@@ -1185,22 +948,24 @@ class Context:
         this context's device for device / resident columns or out_device=True, else a numpy array; None with
         want_codes=False) and the int64 rows per code as a numpy array of n_bins + 2, the bins, then NONE, then NAN (None
         with want_counts=False)."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         n = int(n_rows)
         e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         n_bins = e.shape[0] - 1
         if not want_codes and not want_counts:
             raise ValueError("bin: neither codes nor counts asked for")
-        out, out_device = self._codes_out(n, sp, out, out_device, want_codes)
+        if want_codes:
+            out, out_device = self._out_buffer(n, np.int32, sp, out, out_device, "n_rows")
+        elif out is not None:
+            raise ValueError("want_codes=False takes no out")
+        else:
+            out_device = False
         # (no rows: no codes pointer is passed, so the counts stand for "something asked for")
         counts = np.zeros(max(n_bins, 0) + 2, np.int64) if want_counts or n == 0 else None
-        st = self.lib.pandrs_hip_bin(self.h, sp, cc, n, e.ctypes.data_as(C.POINTER(C.c_double)), n_bins,
-                                     L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(out) if n and out is not None else None,
-                                     None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_int64)))
-        if st:
-            _raise(st)
-        return (None if out is None else out[:n]), (counts if want_counts else None)
+        _check(self.lib.pandrs_hip_bin(self.h, sp, cc, n, e.ctypes.data_as(C.POINTER(C.c_double)), n_bins, _space(out_device),
+                                       _ptr(out) if n and out is not None else None,
+                                       None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out, (counts if want_counts else None)
 
     # -- distinct values and their counts (an LDS table for few distinct integers, else the groupby engine) ----------------
     def distinct(self, col, n_rows, order, code_rank=None, out_device=False):
@@ -1213,44 +978,21 @@ class Context:
         -> (values, flags, counts, info): uint64 cells (the i64, the f64 bits, the code, 0 / 1), uint8 flags (L.DISTINCT_NUMBER,
         L.DISTINCT_NAN, L.DISTINCT_NULL), exact int64 counts - numpy arrays, or with out_device torch tensors on this context's
         device (values as int64 bit patterns) - and the L.DistinctInfo of the call as a dict."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
-        rank, n_codes = None, 0
-        if code_rank is not None:
-            if sp == L.MEM_DEVICE:
-                import torch
-                rank = code_rank if _is_torch(code_rank) else torch.from_numpy(
-                    np.ascontiguousarray(code_rank, dtype=np.uint32).view(np.int32)).to("cuda:%d" % self.device)
-                if _is_torch(code_rank):
-                    self._wait_for_producer()
-            else:
-                rank = np.ascontiguousarray(code_rank.cpu().numpy() if _is_torch(code_rank) else code_rank).view(np.uint32)
-            keep.append(rank)
-            n_codes = int(rank.numel() if _is_torch(rank) else rank.shape[0])
+        cc, sp, keep = self._col(col)
+        rank, n_codes = self._code_rank(code_rank, sp, keep)
         info = L.DistinctInfo()
-        st = self.lib.pandrs_hip_distinct(self.h, sp, cc, int(n_rows), int(order), _ptr(rank), n_codes, C.byref(info))
-        if st:
-            _raise(st)
+        _check(self.lib.pandrs_hip_distinct(self.h, sp, cc, int(n_rows), int(order), _ptr(rank), n_codes, C.byref(info)))
         values, flags, counts = self.distinct_fetch(info.n_entries, out_device)
         return values, flags, counts, {name: getattr(info, name) for name, _ in L.DistinctInfo._fields_ if name != "reserved"}
 
     def distinct_fetch(self, n_entries, out_device=False, values=True, flags=True, counts=True):
         """The list the last distinct call left in the context (until the next compute call on it), or the parts asked for."""
         n = int(n_entries)
-        if out_device:
-            import torch
-            dev = "cuda:%d" % self.device
-            v = torch.empty(n, dtype=torch.int64, device=dev) if values else None
-            f = torch.empty(n, dtype=torch.uint8, device=dev) if flags else None
-            k = torch.empty(n, dtype=torch.int64, device=dev) if counts else None
-        else:
-            v = np.empty(n, np.uint64) if values else None
-            f = np.empty(n, np.uint8) if flags else None
-            k = np.empty(n, np.int64) if counts else None
-        st = self.lib.pandrs_hip_distinct_fetch(self.h, L.MEM_DEVICE if out_device else L.MEM_HOST, _ptr(v) if n else None,
-                                                _ptr(f) if n else None, _ptr(k) if n else None)
-        if st:
-            _raise(st)
+        v = self._empty(n, np.uint64, out_device) if values else None
+        f = self._empty(n, np.uint8, out_device) if flags else None
+        k = self._empty(n, np.int64, out_device) if counts else None
+        _check(self.lib.pandrs_hip_distinct_fetch(self.h, _space(out_device), _ptr(v) if n else None,
+                                                  _ptr(f) if n else None, _ptr(k) if n else None))
         return v, f, k
 
     # -- derived columns (one postfix program over up to eight columns, one stream) ---------------------------------------
@@ -1267,9 +1009,7 @@ class Context:
     def _eval_check(dtypes, ops, args, n_ops):
         dts = (C.c_int32 * max(len(dtypes), 1))(*[int(d) for d in dtypes])
         is_mask, depth = C.c_int32(0), C.c_int32(0)
-        st = L.load().pandrs_hip_eval_check(dts, len(dtypes), ops, args, n_ops, C.byref(is_mask), C.byref(depth))
-        if st:
-            _raise(st)
+        _check(L.load().pandrs_hip_eval_check(dts, len(dtypes), ops, args, n_ops, C.byref(is_mask), C.byref(depth)))
         return bool(is_mask.value), depth.value
 
     @staticmethod
@@ -1300,18 +1040,14 @@ class Context:
         if is_mask:
             if out_mask is not None:
                 raise ValueError("a boolean program takes no out_mask")
-            out, out_device = self._mask_out(n, sp, out, out_device, False)
-            st = self.lib.pandrs_hip_eval(self.h, sp, cc, len(cols), n, ops, args, len(program), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                          _ptr(out) if n else None, None, C.byref(cnt))
-            if st:
-                _raise(st)
-            return out[:(n + 7) // 8], cnt.value
-        out, out_mask, out_device = self._cell_outs(n, sp, False, out, out_mask, out_device)
-        st = self.lib.pandrs_hip_eval(self.h, sp, cc, len(cols), n, ops, args, len(program), L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                      _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(cnt))
-        if st:
-            _raise(st)
-        return out[:n], (out_mask[:(n + 7) // 8] if cnt.value else None), cnt.value
+            out, out_device = self._out_buffer((n + 7) // 8, np.uint8, sp, out, out_device, "ceil(n_rows / 8)")
+        else:
+            out, out_mask, out_device = self._cell_outs(n, sp, False, out, out_mask, out_device)
+        _check(self.lib.pandrs_hip_eval(self.h, sp, cc, len(cols), n, ops, args, len(program), _space(out_device),
+                                        _ptr(out) if n else None, _ptr(out_mask) if n else None, C.byref(cnt)))
+        if is_mask:
+            return out, cnt.value
+        return out, (out_mask if cnt.value else None), cnt.value
 
     def isin(self, col, n_rows, values, negate=False, out=None, out_device=None, count_only=False):
         """Membership of every cell of one column in a value list on the device (pandrs_hip_isin; PandasCompatExt::isin /
@@ -1319,8 +1055,7 @@ class Context:
         only).  `col` as in predicate, also U32CODE; `values` is a (data, None, dtype) triple on the host or the device (its
         space is independent of the column's): F64 / F64, I64 / F64 (the cell as f64), I64 / I64 (as integers) or U32CODE /
         U32CODE.  A null cell never matches; `negate` inverts every bit.  -> (bits, count) as predicate."""
-        keep = []
-        cc, sp = self._cols([tuple(col)], keep)
+        cc, sp, keep = self._col(col)
         vdata, vmask, vdt = tuple(values)
         if vmask is not None:
             raise ValueError("the value list takes no null mask")
@@ -1329,8 +1064,6 @@ class Context:
         n = int(n_rows)
         out, out_device = self._mask_out(n, sp, out, out_device, count_only)
         cnt = C.c_int64(0)
-        st = self.lib.pandrs_hip_isin(self.h, sp, cc, n, vsp, vc, n_values, 1 if negate else 0, L.MEM_DEVICE if out_device else L.MEM_HOST,
-                                      _ptr(out) if n else None, C.byref(cnt))
-        if st:
-            _raise(st)
-        return (None if out is None else out[:(n + 7) // 8]), cnt.value
+        _check(self.lib.pandrs_hip_isin(self.h, sp, cc, n, vsp, vc, n_values, 1 if negate else 0, _space(out_device),
+                                        _ptr(out) if n else None, C.byref(cnt)))
+        return out, cnt.value
