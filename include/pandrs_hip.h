@@ -224,6 +224,9 @@ int32_t pandrs_hip_workspace_poisoned_bytes(int64_t *out_bytes);
  *   "distinct_path"     tests / experiments: 1 = pandrs_hip_distinct takes the direct (LDS table) path wherever the column's numbers fit
  *                       it, 2 = it always takes the groupby engine; 0 = the default, direct wherever it fits (the same list;
  *                       experiments/distinct_bench.py)
+ *   "pivot_path"        tests / experiments: 1 = pandrs_hip_pivot takes the direct (LDS table) path wherever the two key columns fit it,
+ *                       2 = it always takes the general path (the groupby engine); 0 = the default, direct wherever it fits (the
+ *                       same result; experiments/pivot_bench.py)
  *   "window_quantile_path"  tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, which serves rolling
  *                       windows of at most 44 rows (a wider or expanding window: PANDRS_HIP_ERR_INVALID_ARGUMENT), 2 = it always
  *                       takes the general (wavelet matrix) path; 0 = the default, by the window (experiments/window_quantile_bench.py)
@@ -1089,7 +1092,7 @@ int32_t pandrs_hip_bin_edges(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
  * with another dtype or with n_codes == 0, n_codes < 0, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows ==
  * 0: OK, an empty list and all-zero info (a call like any other: it starts and ends a timings record).
  * Out of scope: a call between 2^31 and 2^32 rows is untested (the row arithmetic is 64-bit by construction); per-row codes
- * (to_categorical), duplicated / drop_duplicates, crosstab; the multi-GPU path. */
+ * (to_categorical), duplicated / drop_duplicates; the multi-GPU path.  (crosstab is pandrs_hip_pivot, below.) */
 typedef enum pandrs_hip_distinct_order { PANDRS_HIP_DISTINCT_BY_VALUE = 0, PANDRS_HIP_DISTINCT_BY_COUNT = 1 } pandrs_hip_distinct_order;
 
 typedef struct pandrs_hip_distinct_info {
@@ -1107,6 +1110,112 @@ int32_t pandrs_hip_distinct(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs
 /* any pointer may be NULL */
 int32_t pandrs_hip_distinct_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, uint64_t *out_values, uint8_t *out_flags,
                                   int64_t *out_counts);
+
+/* ---- a group-by over two key columns laid out as a dense matrix: crosstab, pivot_table, pivot / unstack ---------------------------
+ * PandasCompatExt::crosstab (src/dataframe/pandas_compat/functions.rs:2138-2183), PivotTable with AggFunction Sum / Mean / Min / Max /
+ * Count (src/pivot/mod.rs:12-250) and pivot / unstack (functions.rs:2471-2527).  The reference collects
+ * HashMap<(String, String), Vec<f64>> with one string clone per row; here pandrs_hip_pivot computes the labels of either key column
+ * and the R x C cells on the device and keeps them in the context, pandrs_hip_pivot_fetch copies them out (two steps, as distinct /
+ * distinct_fetch: the caller allocates after it knows R and C).
+ * Labels: key columns may be I64, F64, U32CODE (with an optional rank table) or BOOLBITS, with or without null masks.  The labels
+ * of a column are its distinct numbers in pandrs_hip_distinct's BY_VALUE order (the order-preserving image of the bits: I64 as
+ * signed integers; F64 -inf .. -0.0, 0.0 .. +inf, so -0.0 before 0.0; BOOLBITS false, true; U32CODE by rank[code] when the rank
+ * table - n_codes uint32, a permutation: the byte-wise string order - is given, else by code), as 8-byte cells with flag 0; after
+ * the numbers comes at most ONE missing label with flag 1 and cell 0: NaN cells and null cells of a key column form the same label
+ * (the reference sees both as one string), and a cell under a null bit is never looked at.  With n_codes > 0 a code >= n_codes is
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT, found on the device with no fault, and the context serves the next call.
+ * Cells: column-major, cell (index label i, columns label j) at [j * R + i]: the frame's output columns are per columns label.
+ * out_rows[j * R + i] is the number of rows holding the pair, exact, as int64; 0 = the cell is absent; this is crosstab's answer,
+ * and the rows sum to n_rows.  out_cells is NaN (0x7FF8000000000000) for an absent cell and otherwise what the groupby engine's
+ * Sum / Mean / Min / Max / Count / Last (pandrs_hip_groupby_agg over the two key columns) gives for the group
+ * (index label, columns label) of values_col, an I64 or F64 column with or without a mask: null value cells are skipped; Sum of
+ * an I64 column wraps and is converted once; Mean divides by the non-null cells and is 0.0 when there is none; Min / Max skip NaN
+ * cells, order -0.0 < 0.0, and answer 0.0 when no cell counts or the extreme is the sentinel (+inf / -inf, I64_MAX / I64_MIN);
+ * Count is the rows of the cell, null and NaN value cells included; Last is the value at the cell's last row, 0.0 when it is
+ * null.  PANDRS_HIP_PIVOT_ROWS (crosstab) takes no values column and out_cells holds the rows as doubles.
+ * Min, Max, Count, Last and out_rows are bit for bit the engine's on both paths; Sum and Mean of F64 stay within the bound of the
+ * device sums, 2 gamma_k sum|x| over the cell's own k rows, and are exact for I64 whose partial sums stay below 2^53.
+ * Deviations (pivot/mod.rs:195-228, functions.rs:2492-2499, against the contract above): the reference's Count is values.len(), so it
+ * counts NaN value cells, as here; its Min / Max are a fold from the first value with `if x < y` / `if x > y`, which keeps a
+ * leading NaN and the earlier of -0.0 / 0.0 (here NaN cells are skipped and -0.0 < 0.0, as in the engine) and returns an extreme of
+ * +inf / -inf as it is (here the engine's sentinel rule answers 0.0); its Sum / Mean fold in row order and divide by every row (here
+ * within the bound above, null value cells skipped); an absent cell is the string "" in its legacy frame (here NaN, and the frame
+ * masks it); its label order for pivot_table is HashSet order (here byte-wise ascending on the host, as in crosstab); pivot /
+ * unstack insert into a HashMap per pair, so the last row of a pair wins: PANDRS_HIP_PIVOT_LAST, a null value cell as 0.0.
+ * How (pivot.hip).  A census of both key columns (distinct.hpp, the census of pandrs_hip_distinct) gives min, max, the missing
+ * counts, F64 integrality and -0.0 presence.  Direct path (info.path 1): both columns addressable by value under the rule of
+ * distinct's direct path (codes and bools by value; I64 by v - min in unsigned 64-bit, so I64_MIN .. I64_MAX does not wrap; F64 by
+ * (int64)v - min, only when all numbers are integral with |v| <= 2^53 and no -0.0 is present) and (span1 + 1) x (span2 + 1) <=
+ * pivot_direct_max_cells, span = max - min + 1 value slots and the + 1 the missing slot.  ONE fused stream (16-byte loads where the
+ * data is 16-byte aligned, 64-bit row arithmetic) reads the two keys and the value of each row and accumulates into a
+ * per-workgroup table in LDS in span coordinates; there is no label lookup in the stream.  Lanes of a wave that hold the same
+ * cell combine by ballot and a wave reduction before touching LDS, the rest use LDS atomics, so one hot cell does not
+ * serialise; a per-workgroup uint32 counter cannot overflow below 2^32 rows; non-empty cells are folded into 64-bit / f64
+ * workspace cells when the workgroup ends.  LAST keeps the largest row index per cell and the finish kernel gathers the value.
+ * One small finish kernel drops span rows and span columns with no row (which yields the labels, ranked codes ordered by rank),
+ * writes the dense R x C result and counts n_cells_present.  Key columns are read twice (census, stream), the value column once;
+ * nothing per row is written.  General path (info.path 2), everything else: the groupby engine lists either column's distinct
+ * cells (COUNT, as distinct's engine path) and the radix sort orders them into the label lists; R x C > pivot_max_cells answers
+ * PANDRS_HIP_ERR_OPERATION_FAILED with out_info filled (labels, missing rows, path), nothing retained, and the context serves the
+ * next call; the engine then runs with the two key columns, the op and COUNT, and a small kernel looks each GROUP's two key cells
+ * up in the sorted label lists (a binary search over the order keys) and writes the group into its dense cell; cells no group
+ * reached stay absent.  An F64 key column holding NaN cells gets a bit mask with the NaN cells added (n_rows / 8 bytes), so that
+ * the engine meets one missing group.  No per-row code column is materialised on either path; no workgroup waits for another.
+ * Geometry (tests read it): pivot_direct_max_cells = 4096 table cells, the missing slots included (LDS bytes per 256-thread
+ * workgroup: 4 per cell for ROWS / COUNT, 12 for MIN / MAX / LAST, 16 for SUM / MEAN, so at most 64 KiB: two to four
+ * workgroups per compute unit inside 160 KiB of LDS, more for small tables); pivot_max_cells = 16777216 (16 bytes per retained
+ * cell: the dense result stays at 256 MiB); pivot_tile_rows = 2048 rows per workgroup iteration; pivot_blocks_per_cu = 4;
+ * grid = min(pivot_blocks_per_cu x compute units, ceil(n_rows / pivot_tile_rows)).
+ * "pivot_path" (pandrs_hip_ctx_set_option): 0 = default and 1 = direct wherever it is possible, 2 = always the general path; the
+ * same result either way.  pandrs_hip_get_timings: n_partitions reports the path taken (1 direct, 2 general); the census is
+ * PANDRS_HIP_PHASE_ESTIMATE, the direct stream PANDRS_HIP_PHASE_AGGREGATE.
+ * Retained state: the result stays in the context, in an arena of its own, until the next compute call on it, successful or not
+ * (as the distinct list); pandrs_hip_pivot_fetch without a result is PANDRS_HIP_ERR_INVALID_ARGUMENT, may be repeated, and any of
+ * its pointers may be NULL.  A pandrs_hip_pivot call invalidates the retained groupby result (groupby_fetch / partials_split) and
+ * the distinct list on both paths; the general path also overwrites what pandrs_hip_groupby_agg overwrites: the join result
+ * (join_fetch / join_gather).  The grouping of pandrs_hip_groupby_indices, the filter selection and the shuffle buckets stay.
+ * Buffers: host columns and host rank tables are staged; device and resident columns are read in place.  I64 / F64 data 8-byte
+ * aligned (16 not needed), codes 4-byte aligned, null masks at any byte offset, bits past n_rows ignored.  out_info is a host
+ * pointer.  The fetch's outputs (in out_mem_space) receive R / C labels and flags and R x C cells / rows.
+ * Workspace, sized up front: the two census blocks and three pivot_direct_max_cells tables whatever n_rows; on the direct path
+ * the result for the span table (at most pivot_direct_max_cells cells).  Sized at the stage that needs them: on the general path
+ * the NaN masks after the census, either label list (41 bytes per label) once the engine has counted the column's cells,
+ * groupby_agg's and the sort's workspace, and the dense result (16 bytes per cell, 9 per label) once R and C are known.  A
+ * memory_limit below any of them is PANDRS_HIP_ERR_OUT_OF_MEMORY, which can therefore come after the census or an engine run
+ * (nothing is retained then, and the context serves the next call).  Every block is written before it is read.
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a NULL
+ * index_col / columns_col / out_info, a values column given with PANDRS_HIP_PIVOT_ROWS or missing otherwise, a key dtype outside
+ * I64 / F64 / U32CODE / BOOLBITS (CELL64 included), a values dtype outside I64 / F64, an op outside the enum, a rank table with
+ * another dtype or with n_codes == 0, n_codes < 0, n_rows < 0 or n_rows >= 2^32: PANDRS_HIP_ERR_INVALID_ARGUMENT.  n_rows == 0: OK,
+ * an empty result (R = C = 0) and all-zero info (a call like any other: it starts and ends a timings record).
+ * Out of scope: to_categorical (its first-appearance codes need another pass); duplicated / drop_duplicates; more than one
+ * index, columns or values column; margins; the legacy string frame; the multi-GPU path; a call between 2^31 and 2^32 rows is
+ * untested (the row arithmetic is 64-bit by construction). */
+typedef enum pandrs_hip_pivot_op {
+    PANDRS_HIP_PIVOT_ROWS = 0,   /* crosstab: rows per cell, values_col must be NULL */
+    PANDRS_HIP_PIVOT_SUM = 1,
+    PANDRS_HIP_PIVOT_MEAN = 2,
+    PANDRS_HIP_PIVOT_MIN = 3,
+    PANDRS_HIP_PIVOT_MAX = 4,
+    PANDRS_HIP_PIVOT_COUNT = 5,  /* the five of pivot/mod.rs:12-23 */
+    PANDRS_HIP_PIVOT_LAST = 6    /* pivot / unstack: the last row of the pair wins */
+} pandrs_hip_pivot_op;
+
+typedef struct pandrs_hip_pivot_info {
+    int64_t n_index_labels, n_column_labels;   /* R, C */
+    int64_t n_cells_present;                   /* cells with at least one row */
+    int64_t index_missing_rows, column_missing_rows;   /* rows whose index / columns cell is NaN or null */
+    int32_t path;                              /* 1 = direct, 2 = general */
+    int32_t reserved;
+} pandrs_hip_pivot_info;
+
+int32_t pandrs_hip_pivot(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *index_col, const uint32_t *index_rank,
+                         int64_t n_index_codes, const pandrs_hip_column *columns_col, const uint32_t *columns_rank,
+                         int64_t n_columns_codes, const pandrs_hip_column *values_col, int64_t n_rows, int32_t op,
+                         pandrs_hip_pivot_info *out_info);
+/* any pointer may be NULL */
+int32_t pandrs_hip_pivot_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, uint64_t *out_index_labels, uint8_t *out_index_flags,
+                               uint64_t *out_column_labels, uint8_t *out_column_flags, double *out_cells, int64_t *out_rows);
 
 /* ---- running folds and lagged differences of one numeric column: cumsum, cumprod, cummax, cummin, cumcount, shift, diff ------
  * PandasCompatExt::cumsum / cumprod / cummax / cummin (src/dataframe/pandas_compat/functions.rs:280-327), shift (:328-342),

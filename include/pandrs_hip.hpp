@@ -15,6 +15,7 @@
 //                             nlargest / nsmallest / idxmax / idxmin: functions.rs:159-192
 //                             value_range / cut / qcut: functions.rs:2270-2282, :2339-2420
 //                             value_counts / unique / nunique / mode_* / is_unique: functions.rs:343-384, :775-788, :1709-1753, :4120-4139, :4226-4259
+//                             crosstab / pivot / unstack: functions.rs:2138-2183, :2471-2527; pivot_table / AggFunction: src/pivot/mod.rs:12-250
 //                             gt / ge / lt / le / eq_value / ne_value: pandas_compat/helpers/comparison_ops.rs:7-46;
 //                             between / is_between / isna / notna / is_finite / is_infinite / isin / isin_numeric /
 //                             query_* / dropna / count_na / has_nulls / count_value: functions.rs:141-158, :253-257,
@@ -255,6 +256,22 @@ struct StatDescribe {
 enum class AggregateOp { Sum = 0, Mean, Min, Max, Count, Std, Var, Median, First, Last, Custom,   // types.rs:11-34
                          Nunique };   // + the legacy AggFunc::Nunique (src/dataframe/groupby.rs:41)
 enum class JoinType { Inner = 0, Left, Right, Outer };                                              // join.rs:11-20
+// AggFunction (src/pivot/mod.rs:12-48), same order; agg_function_name / agg_function_from_str are its name() / from_str()
+enum class AggFunction { Sum = 0, Mean, Min, Max, Count };
+inline const char *agg_function_name(AggFunction f) {
+    static const char *const names[] = {"sum", "mean", "min", "max", "count"};
+    return names[(int)f];
+}
+inline bool agg_function_from_str(std::string s, AggFunction *out) {
+    for (auto &ch : s) ch = (char)std::tolower((unsigned char)ch);
+    if (s == "sum") *out = AggFunction::Sum;
+    else if (s == "mean" || s == "avg" || s == "average") *out = AggFunction::Mean;
+    else if (s == "min" || s == "minimum") *out = AggFunction::Min;
+    else if (s == "max" || s == "maximum") *out = AggFunction::Max;
+    else if (s == "count") *out = AggFunction::Count;
+    else return false;
+    return true;
+}
 
 class GroupBy;
 
@@ -530,6 +547,56 @@ public:
     bool is_unique(const std::string &column_name) const {
         const pandrs_hip_distinct_info info = distinct(column_name, PANDRS_HIP_DISTINCT_BY_VALUE).info;
         return (int64_t)numbers_of(info) == info.n_valid;
+    }
+    // crosstab / pivot_table / pivot / unstack (PandasCompatExt::crosstab, functions.rs:2138-2183; DataFrame::pivot_table,
+    // src/pivot/mod.rs:107-250; unstack / pivot, functions.rs:2471-2527): one pandrs_hip_pivot call each, the small label x label
+    // matrix put into byte-wise string order on the host.  The result: a String column named like the index column with the
+    // distinct index strings ascending, and one Float64 column per distinct columns string, ascending.  A label is stringified
+    // as in value_counts; a missing cell reads "NaN" (numeric) or "" (String, Boolean).  crosstab: the rows per pair, 0.0 where
+    // there is none; a missing label that reads like a literal label of its column is merged with it (the counts add), for the
+    // other methods that is Error::OperationFailed.  pivot_table: the engine's Sum / Mean / Min / Max / Count of the pair's rows
+    // (pandrs_hip.h), a null mask on the cells no row reaches (deviation: the reference's legacy frame writes strings, "" there,
+    // and its label order is HashSet order).  unstack / pivot: the value of the pair's LAST row, NaN where there is none, no
+    // mask.  Before any device call: ColumnNotFound, Type (a values column that is not numeric); a columns label equal to the
+    // index column's name: DuplicateColumnName.
+    OptimizedDataFrame crosstab(const std::string &col1, const std::string &col2) const {
+        const PivotMatrix m = pivot_matrix(col1, col2, nullptr, PANDRS_HIP_PIVOT_ROWS, "crosstab");
+        OptimizedDataFrame out;
+        out.add_column(col1, StringColumn(m.index));
+        for (size_t j = 0; j < m.columns.size(); j++) {
+            std::vector<double> v(m.index.size());
+            for (size_t i = 0; i < v.size(); i++) v[i] = (double)m.rows[j * m.index.size() + i];
+            out.add_column(m.columns[j], Float64Column(std::move(v)));
+        }
+        return out;
+    }
+    OptimizedDataFrame pivot_table(const std::string &index, const std::string &columns, const std::string &values, AggFunction aggfunc) const {
+        static const int32_t ops[] = {PANDRS_HIP_PIVOT_SUM, PANDRS_HIP_PIVOT_MEAN, PANDRS_HIP_PIVOT_MIN, PANDRS_HIP_PIVOT_MAX, PANDRS_HIP_PIVOT_COUNT};
+        const PivotMatrix m = pivot_matrix(index, columns, &values, ops[(int)aggfunc], "pivot_table");
+        OptimizedDataFrame out;
+        out.add_column(index, StringColumn(m.index));
+        for (size_t j = 0; j < m.columns.size(); j++) {
+            const size_t R = m.index.size();
+            std::vector<double> v(m.cells.begin() + j * R, m.cells.begin() + (j + 1) * R);
+            std::vector<bool> nulls(R);
+            bool any = false;
+            for (size_t i = 0; i < R; i++) { nulls[i] = m.rows[j * R + i] == 0; any = any || nulls[i]; }
+            out.add_column(m.columns[j], any ? Float64Column::with_nulls(std::move(v), nulls) : Float64Column(std::move(v)));
+        }
+        return out;
+    }
+    OptimizedDataFrame unstack(const std::string &index_col, const std::string &columns_col, const std::string &values_col) const {
+        const PivotMatrix m = pivot_matrix(index_col, columns_col, &values_col, PANDRS_HIP_PIVOT_LAST, "unstack");
+        OptimizedDataFrame out;
+        out.add_column(index_col, StringColumn(m.index));
+        for (size_t j = 0; j < m.columns.size(); j++) {
+            const size_t R = m.index.size();
+            out.add_column(m.columns[j], Float64Column(std::vector<double>(m.cells.begin() + j * R, m.cells.begin() + (j + 1) * R)));
+        }
+        return out;
+    }
+    OptimizedDataFrame pivot(const std::string &index, const std::string &columns, const std::string &values) const {
+        return unstack(index, columns, values);                      // functions.rs:2524-2527
     }
     // cumsum / cumprod / cummax / cummin / cumcount / shift / diff / pct_change (PandasCompatExt,
     // src/dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094): the reference's vectors from one
@@ -1270,6 +1337,65 @@ private:
             if (e.first == as) { e.second += missing; return out; }
         out.emplace_back(as, missing);
         return out;
+    }
+    // the result of one pandrs_hip_pivot call in byte-wise string order: index / columns strings, cells and rows column-major
+    struct PivotMatrix {
+        std::vector<std::string> index, columns;
+        std::vector<double> cells;         // [j * index.size() + i]
+        std::vector<int64_t> rows;
+    };
+    // the strings of one dimension's labels and, per output label in ascending order, the device labels that form it
+    static std::vector<std::vector<size_t>> pivot_labels(int32_t dtype, const std::vector<uint64_t> &cells, const std::vector<uint8_t> &flags,
+                                                         bool counts_add, const char *what, std::vector<std::string> *names) {
+        std::map<std::string, std::vector<size_t>> groups;          // (std::string compares byte-wise)
+        const std::string missing = dtype <= PANDRS_HIP_F64 ? "NaN" : "";
+        for (size_t i = 0; i < cells.size(); i++) groups[flags[i] ? missing : detail::key_string(dtype, cells[i], false)].push_back(i);
+        if (groups.size() != cells.size() && !counts_add)
+            throw Error(Error::OperationFailed, std::string(what) + ": a missing cell of the key column reads like its label '" + missing + "'; the two cannot share a cell");
+        std::vector<std::vector<size_t>> take;
+        for (auto &g : groups) { names->push_back(g.first); take.push_back(g.second); }
+        return take;
+    }
+    PivotMatrix pivot_matrix(const std::string &index, const std::string &columns, const std::string *values, int32_t op, const char *what) const {
+        const Column &ic = column(index), &cc = column(columns);
+        if (values) numeric(*values);
+        PivotMatrix m;
+        if (!row_count_) return m;
+        const pandrs_hip_column iv = view_of(index), cv = view_of(columns);
+        pandrs_hip_column vv{};
+        if (values) vv = view_of(*values);
+        const bool strings = ic.index() == 2 || cc.index() == 2;
+        std::vector<uint32_t> rank = strings ? StringPool::global().rank_table() : std::vector<uint32_t>{};
+        const uint32_t *rank_ptr = rank.data();
+        detail::Staged staged_rank;
+        if (strings && is_resident()) rank_ptr = staged_rank.upload(rank);     // one memory space per call
+        pandrs_hip_pivot_info info{};
+        detail::check(pandrs_hip_pivot(detail::context(), mem_space(), &iv, ic.index() == 2 ? rank_ptr : nullptr, ic.index() == 2 ? (int64_t)rank.size() : 0,
+                                       &cv, cc.index() == 2 ? rank_ptr : nullptr, cc.index() == 2 ? (int64_t)rank.size() : 0, values ? &vv : nullptr,
+                                       (int64_t)row_count_, op, &info));
+        const size_t R = (size_t)info.n_index_labels, C = (size_t)info.n_column_labels;
+        std::vector<uint64_t> il(R), cl(C);
+        std::vector<uint8_t> fi(R), fc(C);
+        std::vector<double> cells(R * C);
+        std::vector<int64_t> rows(R * C);
+        detail::check(pandrs_hip_pivot_fetch(detail::context(), PANDRS_HIP_MEM_HOST, il.data(), fi.data(), cl.data(), fc.data(), cells.data(), rows.data()));
+        const bool add = op == PANDRS_HIP_PIVOT_ROWS;
+        const auto itake = pivot_labels(detail::col_dtype(ic), il, fi, add, what, &m.index);
+        const auto ctake = pivot_labels(detail::col_dtype(cc), cl, fc, add, what, &m.columns);
+        for (auto &name : m.columns)
+            if (name == index) throw Error(Error::DuplicateColumnName, index);
+        const size_t Ro = itake.size(), Co = ctake.size();
+        m.cells.assign(Ro * Co, 0.0);
+        m.rows.assign(Ro * Co, 0);
+        for (size_t j = 0; j < Co; j++)
+            for (size_t i = 0; i < Ro; i++) {
+                int64_t n = 0;
+                for (size_t sj : ctake[j])
+                    for (size_t si : itake[i]) n += rows[sj * R + si];
+                m.rows[j * Ro + i] = n;
+                m.cells[j * Ro + i] = add ? (double)n : cells[ctake[j][0] * R + itake[i][0]];
+            }
+        return m;
     }
     pandrs_hip_column_stats stats(const std::string &name) const {
         const Column &c = column(name);

@@ -39,6 +39,8 @@ BIN_CUT, BIN_QCUT = range(2)
 BIN_NONE, BIN_NAN, BIN_MAX_BINS = -1, -2, 4096
 DISTINCT_BY_VALUE, DISTINCT_BY_COUNT = range(2)
 DISTINCT_NUMBER, DISTINCT_NAN, DISTINCT_NULL = range(3)        # the flags of a distinct entry
+PIVOT_ROWS, PIVOT_SUM, PIVOT_MEAN, PIVOT_MIN, PIVOT_MAX, PIVOT_COUNT, PIVOT_LAST = range(7)
+PIVOT_NUMBER, PIVOT_MISSING = range(2)                          # the flags of a pivot label
 OK, ERR_INVALID_ARGUMENT, ERR_TYPE_MISMATCH, ERR_OPERATION_FAILED, ERR_COMPUTATION, \
     ERR_OUT_OF_MEMORY, ERR_NOT_INITIALIZED, ERR_BELOW_THRESHOLD = range(8)
 
@@ -89,6 +91,11 @@ class DescribeStats(C.Structure):          # pandrs_hip_describe_stats
 class DistinctInfo(C.Structure):           # pandrs_hip_distinct_info
     _fields_ = [("n_entries", C.c_int64), ("n_valid", C.c_int64), ("nan_count", C.c_int64), ("null_count", C.c_int64),
                 ("max_count", C.c_int64), ("n_modes", C.c_int64), ("path", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PivotInfo(C.Structure):              # pandrs_hip_pivot_info
+    _fields_ = [("n_index_labels", C.c_int64), ("n_column_labels", C.c_int64), ("n_cells_present", C.c_int64),
+                ("index_missing_rows", C.c_int64), ("column_missing_rows", C.c_int64), ("path", C.c_int32), ("reserved", C.c_int32)]
 
 
 # pandrs_hip_transport: the exchange's collectives as host callbacks (pandrs_hip_comm_adopt_transport)
@@ -193,6 +200,9 @@ SYMBOLS = {
                                          C.POINTER(C.c_int64)]),
     "pandrs_hip_distinct": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(DistinctInfo)]),
     "pandrs_hip_distinct_fetch": (C.c_int32, [_P, C.c_int32, _P, _P, _P]),
+    "pandrs_hip_pivot": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), _P, C.c_int64, C.POINTER(Column), _P, C.c_int64, C.POINTER(Column),
+                                      C.c_int64, C.c_int32, C.POINTER(PivotInfo)]),
+    "pandrs_hip_pivot_fetch": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "pandrs_hip_topk": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pandrs_hip_arg_extreme": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

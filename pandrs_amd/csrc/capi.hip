@@ -98,7 +98,7 @@ int32_t pandrs_hip_ctx_destroy(pandrs_hip_ctx *c) try {
     if (!c) return PANDRS_HIP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release(); c->topk.release(); c->dn_arena.release();
+    c->work.release(); c->result.release(); c->staging.release(); c->temp.release(); c->result2.release(); c->result3.release(); c->side.release(); c->super.release(); c->packed.release(); c->pairs.release(); c->groups.release(); c->shuf.release(); c->absorb.release(); c->overflow.release(); c->filt.release(); c->win.release(); c->topk.release(); c->dn_arena.release(); c->pv_arena.release(); c->pv_mask.release(); c->pv_lab0.release(); c->pv_lab1.release();
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) { (void)hipEventDestroy(c->ev_begin[i]); (void)hipEventDestroy(c->ev_end[i]); }
     (void)hipEventDestroy(c->ev_call_begin); (void)hipEventDestroy(c->ev_call_end);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -264,6 +264,7 @@ int32_t pandrs_hip_ctx_set_option(pandrs_hip_ctx *c, const char *name, int64_t v
     else if (!std::strcmp(name, "predicate_path")) c->opt.predicate_path = value;
     else if (!std::strcmp(name, "bin_path")) c->opt.bin_path = value;
     else if (!std::strcmp(name, "distinct_path")) c->opt.distinct_path = value;
+    else if (!std::strcmp(name, "pivot_path")) c->opt.pivot_path = value;
     else if (!std::strcmp(name, "window_quantile_path")) c->opt.window_quantile_path = value;
     else return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return PANDRS_HIP_OK;
@@ -613,6 +614,22 @@ int32_t pandrs_hip_distinct_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, ui
     if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "distinct_fetch: no context");
     return pandrs::distinct_fetch_entry(ctx, out_mem_space, out_values, out_flags, out_counts);
 } catch (...) { return pandrs::on_exception("pandrs_hip_distinct_fetch"); }
+
+int32_t pandrs_hip_pivot(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *index_col, const uint32_t *index_rank,
+                         int64_t n_index_codes, const pandrs_hip_column *columns_col, const uint32_t *columns_rank, int64_t n_columns_codes,
+                         const pandrs_hip_column *values_col, int64_t n_rows, int32_t op, pandrs_hip_pivot_info *out_info) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "pivot: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::pivot_entry(ctx, mem_space, index_col, index_rank, n_index_codes, columns_col, columns_rank, n_columns_codes, values_col,
+                               n_rows, op, out_info);
+} catch (...) { return pandrs::on_exception("pandrs_hip_pivot"); }
+
+int32_t pandrs_hip_pivot_fetch(pandrs_hip_ctx *ctx, int32_t out_mem_space, uint64_t *out_index_labels, uint8_t *out_index_flags,
+                               uint64_t *out_column_labels, uint8_t *out_column_flags, double *out_cells, int64_t *out_rows) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "pivot_fetch: no context");
+    return pandrs::pivot_fetch_entry(ctx, out_mem_space, out_index_labels, out_index_flags, out_column_labels, out_column_flags, out_cells,
+                                     out_rows);
+} catch (...) { return pandrs::on_exception("pandrs_hip_pivot_fetch"); }
 
 int32_t pandrs_hip_eval(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
                         const int32_t *ops, const double *args, int32_t n_ops, int32_t out_mem_space, void *out_data, uint8_t *out_null_mask,

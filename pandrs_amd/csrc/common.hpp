@@ -215,6 +215,17 @@ struct DistinctResult {
     int64_t *counts = nullptr;
 };
 
+// the result of the last pandrs_hip_pivot (pivot.hip), in the `pv_arena`: the labels of either dimension (8-byte cells, flag 1 = the
+// missing label), the R x C cells and rows per cell, column-major; retained like the distinct list
+struct PivotResult {
+    bool valid = false;
+    int64_t R = 0, C = 0;
+    uint64_t *ilab = nullptr, *clab = nullptr;
+    uint8_t *iflag = nullptr, *cflag = nullptr;
+    double *cells = nullptr;
+    int64_t *rows = nullptr;
+};
+
 struct Options {
     int64_t groups_hint = 0;     // 0 = estimate from a sample
     int64_t scatter_staged = 1;  // stage columns through LDS for coalesced partition writes
@@ -269,6 +280,7 @@ struct Options {
     int64_t predicate_path = 0;      // tests / experiments: 1 = pandrs_hip_predicate converts every I64 cell with (double)v in the loop instead of comparing integers against the bisected interval
     int64_t bin_path = 0;            // tests / experiments: 1 = pandrs_hip_bin always searches, 2 = it guesses wherever the edges are evenly spaced (0 = the guess from bin_guess_min_bins bins on)
     int64_t distinct_path = 0;       // tests / experiments: 1 = pandrs_hip_distinct takes the direct (LDS table) path wherever the numbers fit it, 2 = always the engine (0 = direct wherever it fits)
+    int64_t pivot_path = 0;          // tests / experiments: 1 = pandrs_hip_pivot takes the direct (LDS table) path wherever the two key columns fit it, 2 = always the general path (0 = direct wherever it fits)
     int64_t window_quantile_path = 0;   // tests / experiments: 1 = pandrs_hip_window_quantile takes the direct (LDS) path, 2 = the general (wavelet matrix) path (0 = by the window)
     int64_t agg_ablate = 0;          // experiments: 1 no min/max, 2 lookup only, 3 stream only (C2 profile of aggregate2)
 };
@@ -325,6 +337,9 @@ struct pandrs_hip_ctx {
     int n_cu = 0;
     pandrs::Arena dn_arena;      // the retained distinct list and its unsorted form (distinct.hip)
     pandrs::DistinctResult dn;
+    pandrs::Arena pv_arena;      // the retained pivot result (pivot.hip)
+    pandrs::Arena pv_mask, pv_lab0, pv_lab1;   // its general path: key masks with the NaN cells added, either column's label lists
+    pandrs::PivotResult pv;
 };
 
 namespace pandrs {
@@ -342,9 +357,10 @@ struct PhaseTimer {
     ~PhaseTimer() { if (!c->quiet) (void)hipEventRecord(c->ev_end[phase], c->stream); }
 };
 
-// (every compute call begins here: the distinct list is retained "until the next compute call", pandrs_hip.h)
+// (every compute call begins here: the distinct list and the pivot result are retained "until the next compute call", pandrs_hip.h)
 inline void timings_begin(pandrs_hip_ctx *c) {
     c->dn.valid = false;
+    c->pv.valid = false;
     std::memset(&c->timings, 0, sizeof c->timings);
     for (int i = 0; i < PANDRS_HIP_MAX_PHASES; i++) c->ev_used[i] = false;
     c->timings_lazy = c->timings_pending = false;
@@ -436,6 +452,12 @@ int32_t bin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column 
 int32_t distinct_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t order,
                        const uint32_t *code_rank, int64_t n_codes, pandrs_hip_distinct_info *out_info);
 int32_t distinct_fetch_entry(pandrs_hip_ctx *c, int32_t out_mem_space, uint64_t *out_values, uint8_t *out_flags, int64_t *out_counts);
+// pivot.hip: the two-key group-by of (index_col, columns_col) as a dense label x label matrix; retained in c->pv for the fetch
+int32_t pivot_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *index_col, const uint32_t *index_rank, int64_t n_index_codes,
+                    const pandrs_hip_column *columns_col, const uint32_t *columns_rank, int64_t n_columns_codes,
+                    const pandrs_hip_column *values_col, int64_t n_rows, int32_t op, pandrs_hip_pivot_info *out_info);
+int32_t pivot_fetch_entry(pandrs_hip_ctx *c, int32_t out_mem_space, uint64_t *out_index_labels, uint8_t *out_index_flags,
+                          uint64_t *out_column_labels, uint8_t *out_column_flags, double *out_cells, int64_t *out_rows);
 // rank.hip: the ascending 1-based rank of every row (method = pandrs_hip_rank_method), NaN for NaN and null cells
 int32_t rank_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t method,
                    int32_t out_mem_space, double *out);

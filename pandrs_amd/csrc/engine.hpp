@@ -165,6 +165,11 @@ int32_t build_plan(const int32_t *val_dtypes, const uint8_t *val_has_nulls, int 
                    const pandrs_hip_agg_spec *aggs, int n_aggs, Plan &pl);
 int32_t run_engine(pandrs_hip_ctx *c, const RowSource &rs, const Plan &pl, bool merge, bool partials,
                    int n_aggs, int key_dtype, int n_keys_out = 1, int res_slot = 0);
+// entries.hip: pandrs_hip_groupby_agg between timings_begin and timings_end (the caller holds c->mu and has built `pl` from the
+// value columns and `aggs`): stages host columns, packs a composite key, runs the engine; the result is c->gb
+int32_t groupby_run(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys, int64_t n_rows,
+                    const pandrs_hip_column *vals, int32_t n_vals, const pandrs_hip_agg_spec *aggs, int32_t n_aggs, bool partials,
+                    const Plan &pl);
 // A nested engine run (a merge of partial records, a run over spilled or unplaced rows, a two-level sub-run): it records no phase
 // events and stays off the small / absorb / clustered / two-level paths (c->quiet), and the caller's options, timings and
 // reserve_groups come back when the scope ends: on the normal way out, on an early return (HIP_TRY, ST_TRY) and on unwinding.

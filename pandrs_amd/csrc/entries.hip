@@ -393,6 +393,18 @@ int32_t groupby_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_col
     std::lock_guard<std::mutex> lock(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     timings_begin(c);
+    ST_TRY(groupby_run(c, mem_space, keys, n_keys, n_rows, vals, n_vals, aggs, n_aggs, partials, pl));
+    ST_TRY(timings_end(c));
+    *out_n_groups = c->gb.n_groups;
+    if (out_n_state) *out_n_state = c->gb.n_state;
+    return 0;
+}
+
+// groupby_entry between timings_begin and timings_end, for callers that hold c->mu and keep a record of their own (pivot.hip):
+// staging, the composite key, the engine, the sorted-pass aggregates; the result is c->gb.
+int32_t groupby_run(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *keys, int32_t n_keys, int64_t n_rows,
+                    const pandrs_hip_column *vals, int32_t n_vals, const pandrs_hip_agg_spec *aggs, int32_t n_aggs, bool partials,
+                    const Plan &pl) {
     RowSource rs;
     rs.n_rows = n_rows;
     Stager stg{c, mem_space};
@@ -457,9 +469,6 @@ int32_t groupby_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_col
         for (int s = 0; s < pl.n_src; s++) if (rs.val_null_bits[s]) b += n_rows / 8;
         c->timings.algorithmic_bytes = b;
     }
-    ST_TRY(timings_end(c));
-    *out_n_groups = c->gb.n_groups;
-    if (out_n_state) *out_n_state = c->gb.n_state;
     return 0;
 }
 

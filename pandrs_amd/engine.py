@@ -995,6 +995,44 @@ class Context:
                                                   _ptr(f) if n else None, _ptr(k) if n else None))
         return v, f, k
 
+    # -- a group-by over two key columns as a dense matrix (one fused stream into an LDS table, else the groupby engine) -----
+    def pivot(self, index_col, columns_col, n_rows, op, values_col=None, index_rank=None, columns_rank=None, out_device=False):
+        """The two-key group-by of (index_col, columns_col) laid out as an R x C matrix, on the device (pandrs_hip_pivot +
+        pandrs_hip_pivot_fetch; crosstab, src/dataframe/pandas_compat/functions.rs:2138-2183; pivot_table, src/pivot/mod.rs:12-250;
+        pivot / unstack, functions.rs:2471-2527).  The key columns are (data, mask, dtype) triples of I64 / F64 / U32CODE /
+        BOOLBITS, all on the host or all on the device, or ResidentColumns; `op` an L.PIVOT_* number; `values_col` an I64 / F64
+        column, None for L.PIVOT_ROWS; `index_rank` / `columns_rank` the string pool's rank table, which makes a U32CODE key
+        order its labels by their strings instead of their codes.
+        -> (index_labels, index_flags, column_labels, column_flags, cells, rows, info): uint64 label cells (the i64, the f64
+        bits, the code, 0 / 1) ascending, uint8 flags (1 = the one missing label, last), the cells as a float64 (C, R) array
+        - cells[j, i] belongs to index label i and columns label j, NaN where no row holds the pair - the exact int64 rows per
+        cell in the same shape, numpy arrays or with out_device torch tensors on this context's device (labels as int64 bit
+        patterns), and the L.PivotInfo of the call as a dict."""
+        cols = [tuple(index_col), tuple(columns_col)] + ([tuple(values_col)] if values_col is not None else [])
+        keep = []
+        cc, sp = self._cols(cols, keep)
+        rank1, n_codes1 = self._code_rank(index_rank, sp, keep)
+        rank2, n_codes2 = self._code_rank(columns_rank, sp, keep)
+        info = L.PivotInfo()
+        at = lambda i: C.cast(C.byref(cc, i * C.sizeof(L.Column)), C.POINTER(L.Column))        # noqa: E731
+        _check(self.lib.pandrs_hip_pivot(self.h, sp, at(0), _ptr(rank1), n_codes1, at(1), _ptr(rank2), n_codes2,
+                                         at(2) if values_col is not None else None, int(n_rows), int(op), C.byref(info)))
+        out = self.pivot_fetch(info.n_index_labels, info.n_column_labels, out_device)
+        return out + ({name: getattr(info, name) for name, _ in L.PivotInfo._fields_ if name != "reserved"},)
+
+    def pivot_fetch(self, n_index_labels, n_column_labels, out_device=False, labels=True, cells=True, rows=True):
+        """The result the last pivot call left in the context (until the next compute call on it), or the parts asked for."""
+        r, c = int(n_index_labels), int(n_column_labels)
+        il = self._empty(r, np.uint64, out_device) if labels else None
+        fi = self._empty(r, np.uint8, out_device) if labels else None
+        cl = self._empty(c, np.uint64, out_device) if labels else None
+        fc = self._empty(c, np.uint8, out_device) if labels else None
+        ce = self._empty((c, r), np.float64, out_device) if cells else None
+        ro = self._empty((c, r), np.int64, out_device) if rows else None
+        some = r > 0 and c > 0
+        _check(self.lib.pandrs_hip_pivot_fetch(self.h, _space(out_device), *[_ptr(x) if some else None for x in (il, fi, cl, fc, ce, ro)]))
+        return il, fi, cl, fc, ce, ro
+
     # -- derived columns (one postfix program over up to eight columns, one stream) ---------------------------------------
     @staticmethod
     def eval_check(dtypes, program):

@@ -56,6 +56,22 @@ class RankMethod(IntEnum):           # pandas_compat/types.rs:48-59, same order
     Dense = 4
 
 
+class AggFunction(IntEnum):          # pivot/mod.rs:12-23, same order
+    Sum = 0
+    Mean = 1
+    Min = 2
+    Max = 3
+    Count = 4
+
+    def name(self):                  # pivot/mod.rs:27-35
+        return self._name_.lower()
+
+    @classmethod
+    def from_str(cls, s):            # pivot/mod.rs:38-47: None for a name it does not know
+        return {"sum": cls.Sum, "mean": cls.Mean, "avg": cls.Mean, "average": cls.Mean, "min": cls.Min, "minimum": cls.Min,
+                "max": cls.Max, "maximum": cls.Max, "count": cls.Count}.get(str(s).lower())
+
+
 class JoinType(IntEnum):             # join.rs:11-20
     Inner = 0
     Left = 1
@@ -993,6 +1009,104 @@ class OptimizedDataFrame:
         info = self._distinct(self.column(column), L.DISTINCT_BY_VALUE)[3]
         numbers = info["n_entries"] - (1 if info["nan_count"] else 0) - (1 if info["null_count"] else 0)
         return numbers == info["n_valid"]
+
+    # -- crosstab / pivot_table / pivot / unstack (dataframe/pandas_compat/functions.rs:2138-2183, :2471-2527, ------------
+    #    pivot/mod.rs:12-250): one pandrs_hip_pivot call each, the small label x label matrix ordered on the host -----------
+    def _pivot_labels(self, col, cells, flags, counts_add, what):
+        """The strings of one dimension's labels and the order the reference gives them.  -> (strings, take): `take` lists, per
+        output label in byte-wise ascending order, the device labels that form it.  A label is stringified as value_counts does
+        (an Int64 / Float64 cell's to_string, the pooled string, "true" / "false"); the missing label is "NaN" for a numeric
+        column and "" otherwise.  A missing label that reads like a literal label of the same String / Boolean column is the
+        same string to the reference: the two are merged where counts add (crosstab), and an OperationFailed otherwise."""
+        number = flags == L.PIVOT_NUMBER
+        strings = _key_strings(col.dtype, cells[number], np.zeros(int(number.sum()), np.uint8))
+        if not number.all():
+            strings.append("NaN" if col.dtype in (L.I64, L.F64) else "")
+        groups = {}
+        for i, s in enumerate(strings):
+            groups.setdefault(s, []).append(i)
+        if len(groups) != len(strings) and not counts_add:
+            raise OperationFailed(L.ERR_OPERATION_FAILED, "%s: a missing cell of the key column reads like its label %r; the two "
+                                  "cannot share a cell" % (what, "NaN" if col.dtype in (L.I64, L.F64) else ""))
+        names = sorted(groups, key=str.encode)
+        return names, [groups[s] for s in names]
+
+    def _pivot(self, index, columns, values, op, what):
+        """-> (index column, index strings, column strings, cells (C, R) float64, rows (C, R) int64) of one pandrs_hip_pivot
+        call, rows and columns in byte-wise string order.  ColumnNotFound and type errors come before any device call; a
+        columns label equal to the index column's name is DuplicateColumnName."""
+        icol, ccol = self.column(index), self.column(columns)
+        vcol = None
+        if values is not None:
+            if values not in self.column_indices:
+                raise ColumnNotFound(values)
+            vcol = self._numeric(values)
+        n = self._row_count
+        if n == 0:
+            return icol, [], [], np.empty((0, 0), np.float64), np.empty((0, 0), np.int64)
+        ranks = [GLOBAL_STRING_POOL.rank_table() if c.dtype == L.U32CODE else None for c in (icol, ccol)]
+        il, fi, cl, fc, cells, rows, _ = get_context().pivot(icol.view(), ccol.view(), n, op, None if vcol is None else vcol.view(),
+                                                             index_rank=ranks[0], columns_rank=ranks[1], out_device=False)
+        add = op == L.PIVOT_ROWS
+        inames, itake = self._pivot_labels(icol, np.asarray(il, np.uint64), np.asarray(fi, np.uint8), add, what)
+        cnames, ctake = self._pivot_labels(ccol, np.asarray(cl, np.uint64), np.asarray(fc, np.uint8), add, what)
+        if index in cnames:
+            raise DuplicateColumnName(index)
+        cells, rows = np.asarray(cells, np.float64), np.asarray(rows, np.int64)
+        if add:                                                 # merged labels: their rows add
+            rows = np.stack([rows[t].sum(axis=0) for t in ctake]) if ctake else rows
+            rows = np.stack([rows[:, t].sum(axis=1) for t in itake], axis=1) if itake else rows
+            cells = rows.astype(np.float64)
+        else:
+            cells = cells[[t[0] for t in ctake]][:, [t[0] for t in itake]]
+            rows = rows[[t[0] for t in ctake]][:, [t[0] for t in itake]]
+        return icol, inames, cnames, cells, rows
+
+    def crosstab(self, col1, col2):
+        """PandasCompatExt::crosstab (functions.rs:2138-2183): a String column `col1` with the distinct strings of col1 ascending
+        byte-wise, and one Float64 column per distinct string of col2, ascending, holding the number of rows with that pair
+        (0.0 where there is none).  A missing cell reads "" (String, Boolean) or "NaN" (numeric), as in value_counts."""
+        _, inames, cnames, cells, _ = self._pivot(col1, col2, None, L.PIVOT_ROWS, "crosstab")
+        out = OptimizedDataFrame()
+        out.add_column(col1, StringColumn(inames))
+        for j, name in enumerate(cnames):
+            out.add_column(name, Float64Column(cells[j]))
+        return out
+
+    def pivot_table(self, index, columns, values, aggfunc):
+        """DataFrame::pivot_table (pivot/mod.rs:107-250): a String column `index` with the distinct index strings and one Float64
+        column per distinct columns string holding Sum / Mean / Min / Max / Count of `values` over the rows of the pair, with the
+        engine's fold rules (pandrs_hip.h).  Deviations: the reference's legacy frame writes every cell as a string, "" for a
+        pair without rows - here Float64 columns with a null mask on those cells (the value under it NaN); its label order is
+        HashSet order - here byte-wise ascending, as in crosstab."""
+        if not isinstance(aggfunc, AggFunction):
+            got = AggFunction.from_str(aggfunc)
+            if got is None:
+                raise InvalidValue("unknown aggregation function %r" % (aggfunc,))
+            aggfunc = got
+        op = {AggFunction.Sum: L.PIVOT_SUM, AggFunction.Mean: L.PIVOT_MEAN, AggFunction.Min: L.PIVOT_MIN, AggFunction.Max: L.PIVOT_MAX,
+              AggFunction.Count: L.PIVOT_COUNT}[aggfunc]
+        _, inames, cnames, cells, rows = self._pivot(index, columns, values, op, "pivot_table")
+        out = OptimizedDataFrame()
+        out.add_column(index, StringColumn(inames))
+        for j, name in enumerate(cnames):
+            out.add_column(name, Float64Column.with_nulls(cells[j], rows[j] == 0))
+        return out
+
+    def unstack(self, index_col, columns_col, values_col):
+        """PandasCompatExt::unstack (functions.rs:2471-2522): as crosstab's shape, every cell the value of the LAST row holding the
+        pair (the reference inserts into a HashMap row by row), NaN where no row holds it, no null mask; a null value cell
+        reads 0.0."""
+        _, inames, cnames, cells, _ = self._pivot(index_col, columns_col, values_col, L.PIVOT_LAST, "unstack")
+        out = OptimizedDataFrame()
+        out.add_column(index_col, StringColumn(inames))
+        for j, name in enumerate(cnames):
+            out.add_column(name, Float64Column(cells[j]))
+        return out
+
+    def pivot(self, index, columns, values):
+        """PandasCompatExt::pivot (functions.rs:2524-2527): unstack."""
+        return self.unstack(index, columns, values)
 
     # -- cumulative folds and lags (dataframe/pandas_compat/functions.rs:280-342, :514-541, :2081-2094) ------------
     def _cumulative(self, column_name, op):
