@@ -711,7 +711,7 @@ int32_t pandrs_hip_window_quantile(pandrs_hip_ctx *ctx, int32_t mem_space, const
  * PANDRS_HIP_ERR_OUT_OF_MEMORY.  Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold:
  * PANDRS_HIP_ERR_BELOW_THRESHOLD; a column that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a NULL pointer, n_rows >=
  * 2^32, n_percentiles outside 1 .. 16, a percentile outside [0, 100] or NaN (:176-180): PANDRS_HIP_ERR_INVALID_ARGUMENT.
- * Out of scope: skewness, kurtosis, mode, confidence intervals and outliers of StatisticalSummary. */
+ * Out of scope: mode, confidence intervals and outliers of StatisticalSummary (skewness and kurtosis: pandrs_hip_moments). */
 typedef struct pandrs_hip_describe_stats {
     int64_t count;          /* non-null cells */
     double mean, std, min, q1, median, q3, max;   /* NaN each when count == 0 */
@@ -724,6 +724,120 @@ int32_t pandrs_hip_describe(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs
  * percentiles[j], out_count = the non-null cells.  percentiles / out / out_count are host pointers. */
 int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                              const double *percentiles, int32_t n_percentiles, double *out, int64_t *out_count);
+
+/* ---- shape statistics of whole columns: fused sums of 1 .. 16 columns ---------------------------------------------------------------
+ * Replaces the whole-column statistics of PandasCompatExt that are a few sums over the column: skew / kurtosis
+ * (src/dataframe/pandas_compat/functions.rs:1617-1665), sem / mad / prod / cv / geometric_mean / harmonic_mean
+ * (src/dataframe/pandas_compat/helpers/aggregations.rs:8-51, :108-139, :162-181), var_column / std_column (functions.rs:3571-3588),
+ * range / abs_sum (:4207-4224), the sums behind zscore (:2284-2314) and describe_column (aggregations.rs:54-81), and the per-frame
+ * lists sum_all / mean_all / std_all / var_all / min_all / max_all (:934-1022) and product_all (:1583-1595).  The mirrors restate
+ * each reference expression on the host over the fields below; this entry computes the fields.
+ * The cells that count are neither null nor NaN (every reference function here filters `!v.is_nan()`; a null cell is the
+ * mirrors' missing value), taken as f64 (`v as f64` for I64).  A field whose `want` bit is clear is NaN.
+ * How (moments.hip): the grid is (workgroups, columns); the number of launches does not depend on n_cols.
+ *  1. the first stream (pandrs_hip_describe's: a thread's rows depend on row numbers only) gives the counts, sum, abs_sum, min and
+ *     max, and - only in the kernel variant the `want` bits select - log_sum, recip_sum and prod.  ln and the IEEE divide cost
+ *     tens of f64 instructions per row; a call that asks for none of WANT_LOG / WANT_RECIP / WANT_PROD runs the lean variant.
+ *  2. WANT_CENTRAL only: every workgroup folds its column's partials of step 1 in one fixed order, so all of them hold the
+ *     same bits of mean (a launch-boundary reduce with no launch of its own), then one more stream gives m2, m3, m4 and abs_dev
+ *     together: the column is read twice for all central statistics, not once per statistic.
+ *  3. a small finish kernel folds the partials in that order and writes the structs.
+ * No float atomics anywhere: a result is the same run to run and the same for a host, a device and a resident column.
+ * Geometry (tests read it): moments_tile_rows = 2048 rows per workgroup iteration, moments_blocks_per_cu = 4,
+ * moments_max_columns = 16, grid = (min(moments_blocks_per_cu x compute units, ceil(n_rows / moments_tile_rows)), n_cols)
+ * workgroups of 256 threads, each striding over its column's tiles.
+ * Exactness: the counts, min and max are exact, bit for bit (min / max through the order-preserving code of the f64 value).
+ * mean is sum / count of the returned fields, exactly; the central sums are taken around that mean.  Every sum S = sum t_i
+ * (sum, abs_sum, log_sum, recip_sum, m2, m3, m4, abs_dev) is a parallel fold: with u = 2^-53, gamma_m = m u / (1 - m u) and m =
+ * count, |got - ref| <= (2 gamma_m + 4 u) sum |t_i| against the reference's sequential fold of the same terms (both folds lie
+ * within gamma_m sum |t| of the true sum, as for pandrs_hip_cumulative SUM; a term may round differently by a few ulps: `powi`
+ * against multiplication, the device's ln at 1 ulp against libm).  Integer-valued cells whose mean is an integer and whose
+ * sums stay below 2^53: bit for bit; cells that are +- powers of two: recip_sum and prod bit for bit.
+ * prod: the (mantissa, exponent) state of pandrs_hip_cumulative PROD (frexp / ldexp; 0, +-inf and NaN stay in the mantissa,
+ * where IEEE multiplication gives the reference's class and sign), converted once at the end.  Same contract: wherever every
+ * reference running product is normal, zero by a zero input, infinite by an infinite input, or NaN, the relative error is at
+ * most 2 gamma_m and class and sign are exact.  Same deviation: the reference's sequential fold is sticky after a range
+ * excursion of finite nonzero inputs ([1e200, 1e200, 1e-200, 1e-200] is +inf there); the whole-column product here is the value
+ * the extended-range product rounds to (1.0 for that column), whatever the order of the cells.
+ * Deviations:
+ *  - Signed zero: min and max order -0.0 before +0.0 (pandrs_hip_describe); f64::min / f64::max leave the sign of a zero tie to
+ *    the order of the cells, so a min or max that is zero may differ from the reference in its sign bit only.
+ *  - Null cells: the reference's get_column_numeric_values returns Err on a missing value; here a null cell is skipped like NaN.
+ * n_rows == 0 is status OK: the counts 0, sum and every wanted sum -0.0 (Rust's Sum for f64 starts there), min +inf, max -inf
+ * (the fold identities), prod 1.0, mean NaN.  A column of only null or NaN cells gives the same.
+ * Host columns are staged; device and resident columns are read in place (data 8-byte aligned; a data pointer 8 bytes off a
+ * 16-byte boundary takes its row pairs as two 8-byte loads; each column its own optional null mask at any byte offset, bits
+ * past n_rows ignored).  Workspace: 88 + 32 bytes per (workgroup, column) and the structs; it does not grow with n_rows.
+ * Staging: the host columns.  A memory_limit below either is PANDRS_HIP_ERR_OUT_OF_MEMORY.
+ * pandrs_hip_get_timings: the phase is PANDRS_HIP_PHASE_AGGREGATE; n_partitions names the first stream's variant, 1 + (LOG ? 1 : 0)
+ * + (RECIP ? 2 : 0) + (PROD ? 4 : 0), so 1 is the lean one; table_slots is the number of streams (1, or 2 with WANT_CENTRAL).
+ * Errors: ctx NULL: PANDRS_HIP_ERR_NOT_INITIALIZED; fewer rows than min_size_threshold: PANDRS_HIP_ERR_BELOW_THRESHOLD; a column
+ * that is not I64 / F64: PANDRS_HIP_ERR_TYPE_MISMATCH; a NULL pointer, n_cols outside 1 .. 16, n_rows < 0 or >= 2^32, unknown
+ * `want` bits: PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ * Out of scope: skew / kurtosis as groupby aggregates, corr / cov, mode, confidence intervals. */
+#define PANDRS_HIP_MOMENTS_MAX_COLUMNS 16
+#define PANDRS_HIP_MOMENTS_WANT_CENTRAL 1     /* mean's second stream: m2, m3, m4, abs_dev */
+#define PANDRS_HIP_MOMENTS_WANT_LOG 2         /* log_sum */
+#define PANDRS_HIP_MOMENTS_WANT_RECIP 4       /* recip_sum */
+#define PANDRS_HIP_MOMENTS_WANT_PROD 8        /* prod */
+typedef struct pandrs_hip_moments_stats {
+    int64_t count;          /* cells that are neither null nor NaN (the reference's `valid`) */
+    int64_t count_pos;      /* of them > 0      (geometric_mean's filter, aggregations.rs:110-114) */
+    int64_t count_nonzero;  /* of them != 0.0   (harmonic_mean's filter, :127-131) */
+    double sum, abs_sum;    /* sum x, sum |x| */
+    double min, max;        /* f64::min / f64::max folds from +inf / -inf */
+    double mean;            /* sum / count, the value the central sums were taken around */
+    double m2, m3, m4;      /* sum (x - mean)^2, ^3, ^4          (WANT_CENTRAL) */
+    double abs_dev;         /* sum |x - mean|                     (WANT_CENTRAL) */
+    double log_sum;         /* sum ln x over x > 0                (WANT_LOG) */
+    double recip_sum;       /* sum 1.0 / x over x != 0            (WANT_RECIP) */
+    double prod;            /* product of the valid cells from 1.0 (WANT_PROD) */
+} pandrs_hip_moments_stats;
+
+/* cols: n_cols columns of n_rows rows each; out: n_cols structs on the host, out[i] answers cols[i]. */
+int32_t pandrs_hip_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
+                           uint32_t want, pandrs_hip_moments_stats *out);
+
+/* ---- order statistics by the reference's index rules, and the trimmed mean -------------------------------------------------------
+ * Replaces the sorts of PandasCompatExt::iqr, describe_column's quartiles, percentile_value and trimmed_mean
+ * (src/dataframe/pandas_compat/helpers/aggregations.rs:83-102, :142-159, :184-225) and of median_all
+ * (src/dataframe/pandas_compat/functions.rs:1597-1615).  The reference indexes its sorted `valid` vector, the m cells that are
+ * neither null nor NaN, four ways; none of them is pandrs_hip_quantiles' interpolation:
+ *   AT_FRAC_N      sorted[(usize)(m * a)], NaN when that index is m or more (`get(..).unwrap_or(NAN)`; :87-89, :152-153);
+ *   AT_FRAC_N1     sorted[(usize)((m - 1) * a)] (:198); a outside [0, 1] is NaN (the early return at :185);
+ *   MEDIAN         (sorted[m/2 - 1] + sorted[m/2]) / 2.0 for even m, else sorted[m/2] (functions.rs:1604-1609); its arg is ignored;
+ *   TRIMMED_MEAN   the mean of sorted[t .. m - t), t = (usize)(m * a) (:217-224); a outside [0, 0.5) is NaN (the early return at
+ *                  :204), as is an empty slice (:220-222).
+ * Counting rule: m counts the cells that are neither null nor NaN - unlike pandrs_hip_describe, where NaN cells count and
+ * sort last.  out_count = m.  m == 0 is status OK with NaN results.
+ * How (describe.hip): pandrs_hip_describe's radix select with "ranks by number": the ranks depend on m, which the host does
+ * not know before the first stream, so the one-workgroup ranks kernel evaluates each op's rule on the device from the counts of
+ * that stream, in double as the reference does.  Two ranks per op at the most, so the 1 .. 8 ops of a call never need more than
+ * the select's 32 slots.  TRIMMED_MEAN selects v_lo = sorted[t] and v_hi = sorted[m - 1 - t], then runs one band stream over
+ * the column: the sum of the cells whose order code lies strictly between the two selected codes, and the numbers of cells
+ * below, on the lower code, on the upper code and above.  The finish adds (n_below + n_eq_lo - t) x v_lo + (n_eq_hi + n_above -
+ * t) x v_hi - or (m - 2t) x v_lo when both ranks select one code - and divides by m - 2t, so ties at either cut count exactly as
+ * often as the sorted slice holds them.  The early returns for `a` are decided on the host before any launch.
+ * Geometry: pandrs_hip_describe's (describe_tile_rows, describe_blocks_per_cu); one band stream per TRIMMED_MEAN op.
+ * Exactness: every selected value is bit for bit the element the reference's sort puts at that rank (also I64 beyond 2^53:
+ * the integer is selected, then converted); MEDIAN's and the trimmed mean's arithmetic is the expression above, FMA contraction
+ * off.  The band sum is a parallel fold: |got - ref| <= (2 gamma_k + 4 u) sum |x| over the band's k cells, divided by m - 2t;
+ * integer-valued cells with sums below 2^53: bit for bit.  Deviation: signed zero orders -0.0 before +0.0, as documented for
+ * pandrs_hip_describe.
+ * Host columns are staged; workspace: pandrs_hip_describe's plus 8 x 40 bytes per workgroup; it does not grow with n_rows.
+ * pandrs_hip_get_timings: n_partitions is the number of band streams run.
+ * Errors: as pandrs_hip_describe (NOT_INITIALIZED, BELOW_THRESHOLD, TYPE_MISMATCH, OUT_OF_MEMORY); a NULL pointer, n_rows < 0 or
+ * >= 2^32, n_ops outside 1 .. 8 (more ranks than the select's slots), an unknown op, a NaN `a` (MEDIAN's excepted):
+ * PANDRS_HIP_ERR_INVALID_ARGUMENT.
+ * Out of scope: quantile / percentile with interpolation (functions.rs:735; pandrs_hip_quantiles), mode. */
+#define PANDRS_HIP_ORDER_STATS_MAX_OPS 8
+typedef enum pandrs_hip_order_stat {
+    PANDRS_HIP_OS_AT_FRAC_N = 0, PANDRS_HIP_OS_AT_FRAC_N1 = 1, PANDRS_HIP_OS_MEDIAN = 2, PANDRS_HIP_OS_TRIMMED_MEAN = 3
+} pandrs_hip_order_stat;
+
+/* ops / args / out: n_ops entries each on the host, out[j] answers (ops[j], args[j]); out_count = m. */
+int32_t pandrs_hip_order_stats(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                               const int32_t *ops, const double *args, int32_t n_ops, double *out, int64_t *out_count);
 
 /* ---- rank of one numeric column ---------------------------------------------------------------------------------------------
  * PandasCompatExt::rank(column, RankMethod) (src/dataframe/pandas_compat/functions.rs:193-236, RankMethod at

@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -416,6 +417,184 @@ public:
     // (min_by), NaN and null cells skipped; nullopt when the column holds no number.  One pandrs_hip_arg_extreme pass for both.
     std::optional<size_t> idxmax(const std::string &column_name) const { return arg_extreme(column_name, 1); }
     std::optional<size_t> idxmin(const std::string &column_name) const { return arg_extreme(column_name, 0); }
+    // Shape statistics (PandasCompatExt: skew / kurtosis, src/dataframe/pandas_compat/functions.rs:1617-1665; sem / mad / prod / cv /
+    // geometric_mean / harmonic_mean / iqr / percentile_value / trimmed_mean / describe_column, helpers/aggregations.rs:8-225;
+    // var_column / std_column, functions.rs:3571-3588; range / abs_sum, :4207-4224; zscore, :2284-2314; the *_all lists, :934-1022,
+    // :1583-1615).  Each is the reference's expression, early returns included, over the fields of ONE pandrs_hip_moments call
+    // (asking only for the `want` bits it needs) and / or ONE pandrs_hip_order_stats call.  The cells that count are neither null
+    // nor NaN.  Errors before any device call: ColumnNotFound, Type (a String or Boolean column).
+    pandrs_hip_moments_stats moments(const std::string &column_name, uint32_t want) const {
+        numeric(column_name);
+        pandrs_hip_moments_stats st{};
+        const pandrs_hip_column v = view_of(column_name);
+        detail::check(pandrs_hip_moments(detail::context(), mem_space(), &v, 1, (int64_t)row_count_, want, &st));
+        return st;
+    }
+    struct OrderStat { int32_t op; double arg; };
+    std::pair<std::vector<double>, int64_t> order_stats(const std::string &column_name, const std::vector<OrderStat> &ops) const {
+        numeric(column_name);
+        std::vector<int32_t> op;
+        std::vector<double> arg, out(ops.size());
+        for (const OrderStat &o : ops) { op.push_back(o.op); arg.push_back(o.arg); }
+        int64_t m = 0;
+        const pandrs_hip_column v = view_of(column_name);
+        detail::check(pandrs_hip_order_stats(detail::context(), mem_space(), &v, (int64_t)row_count_, op.data(), arg.data(), (int32_t)op.size(),
+                                             out.data(), &m));
+        return {out, m};
+    }
+    double skew(const std::string &c) const {                                   // functions.rs:1617-1640
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if (st.count < 3) return std::nan("");                                  // :1621
+        const double n = (double)st.count, std_dev = std::sqrt(st.m2 / n);
+        if (std_dev == 0.0) return std::nan("");                                // :1630
+        const double skewness = (st.m3 / n) / ((std_dev * std_dev) * std_dev);
+        return skewness * (std::sqrt(n * (n - 1.0)) / (n - 2.0));               // :1638
+    }
+    double kurtosis(const std::string &c) const {                               // functions.rs:1642-1665
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if (st.count < 4) return std::nan("");                                  // :1646
+        const double n = (double)st.count, std_dev = std::sqrt(st.m2 / n);
+        if (std_dev == 0.0) return std::nan("");                                // :1655
+        const double k = (st.m4 / n) / ((std_dev * std_dev) * (std_dev * std_dev)) - 3.0;
+        return ((n - 1.0) / ((n - 2.0) * (n - 3.0))) * ((n + 1.0) * k + 6.0);   // :1663
+    }
+    double var_column(const std::string &c, size_t ddof = 1) const {            // functions.rs:3571-3584
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if ((size_t)st.count <= ddof) return std::nan("");                      // :3575
+        return st.m2 / ((double)st.count - (double)ddof);
+    }
+    double std_column(const std::string &c, size_t ddof = 1) const { return std::sqrt(var_column(c, ddof)); }      // :3586-3588
+    double sem(const std::string &c, size_t ddof = 1) const {                   // aggregations.rs:8-23
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if ((size_t)st.count <= ddof) return std::nan("");                      // :12
+        return std::sqrt(st.m2 / (double)((size_t)st.count - ddof)) / std::sqrt((double)st.count);
+    }
+    double mad(const std::string &c) const {                                    // aggregations.rs:26-39
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        return st.count ? st.abs_dev / (double)st.count : std::nan("");
+    }
+    double prod(const std::string &c) const {                                   // aggregations.rs:42-51
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_PROD);
+        return st.count ? st.prod : std::nan("");
+    }
+    double range(const std::string &c) const {                                  // functions.rs:4207-4219
+        const auto st = moments(c, 0);
+        return st.count ? st.max - st.min : std::nan("");
+    }
+    double abs_sum(const std::string &c) const { return moments(c, 0).abs_sum; }      // functions.rs:4221-4224
+    double cv(const std::string &c) const {                                     // aggregations.rs:162-181
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if (!st.count) return std::nan("");                                     // :166
+        if (std::fabs(st.mean) < std::numeric_limits<double>::epsilon()) return std::nan("");      // :173
+        return std::sqrt(st.m2 / std::max((double)st.count - 1.0, 1.0)) / std::fabs(st.mean);
+    }
+    double geometric_mean(const std::string &c) const {                         // aggregations.rs:108-122
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_LOG);
+        return st.count_pos ? std::exp(st.log_sum / (double)st.count_pos) : std::nan("");
+    }
+    double harmonic_mean(const std::string &c) const {                          // aggregations.rs:125-139
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_RECIP);
+        return st.count_nonzero ? (double)st.count_nonzero / st.recip_sum : std::nan("");
+    }
+    double iqr(const std::string &c) const {                                    // aggregations.rs:142-159
+        const auto r = order_stats(c, {{PANDRS_HIP_OS_AT_FRAC_N, 0.25}, {PANDRS_HIP_OS_AT_FRAC_N, 0.75}});
+        return r.second < 2 ? std::nan("") : r.first[1] - r.first[0];
+    }
+    // percentile_value / trimmed_mean, two deviations from the reference: the column is looked up first, so a missing or non-numeric
+    // column throws ColumnNotFound / Type even for an argument outside the accepted range (the reference returns NaN there before
+    // it looks at the column); a NaN argument throws InvalidValue (the reference's comparisons let it through, and `NaN as usize`
+    // indexes element 0 / trims nothing).
+    double percentile_value(const std::string &c, double q) const {             // aggregations.rs:184-200
+        numeric(c);
+        if (q != q) throw Error(Error::InvalidValue, "q must not be NaN");
+        if (q < 0.0 || q > 1.0) return std::nan("");                            // :185, before any device call
+        return order_stats(c, {{PANDRS_HIP_OS_AT_FRAC_N1, q}}).first[0];
+    }
+    double trimmed_mean(const std::string &c, double trim_fraction) const {     // aggregations.rs:203-225
+        numeric(c);
+        if (trim_fraction != trim_fraction) throw Error(Error::InvalidValue, "trim_fraction must not be NaN");
+        if (trim_fraction < 0.0 || trim_fraction >= 0.5) return std::nan("");   // :204, before any device call
+        return order_stats(c, {{PANDRS_HIP_OS_TRIMMED_MEAN, trim_fraction}}).first[0];
+    }
+    std::map<std::string, double> describe_column(const std::string &c) const { // aggregations.rs:54-105
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        const double nan = std::nan("");
+        if (!st.count) return {{"count", 0.0}, {"mean", nan}, {"std", nan}, {"min", nan}, {"max", nan}};     // :60-67
+        const double n = (double)st.count;
+        const auto q = order_stats(c, {{PANDRS_HIP_OS_AT_FRAC_N, 0.25}, {PANDRS_HIP_OS_AT_FRAC_N, 0.5}, {PANDRS_HIP_OS_AT_FRAC_N, 0.75}}).first;
+        return {{"count", n}, {"mean", st.mean}, {"std", std::sqrt(st.m2 / std::max(n - 1.0, 1.0))}, {"min", st.min}, {"max", st.max},
+                {"25%", q[0]}, {"50%", q[1]}, {"75%", q[2]}};
+    }
+    std::vector<double> zscore(const std::string &c) const {                    // functions.rs:2284-2314
+        const auto st = moments(c, PANDRS_HIP_MOMENTS_WANT_CENTRAL);
+        if (st.count < 2) throw Error(Error::InvalidValue, "Need at least 2 values for z-score");              // :2288
+        const double std_dev = std::sqrt(st.m2 / ((double)st.count - 1.0));
+        if (std_dev == 0.0) throw Error(Error::InvalidValue, "Standard deviation is zero");                    // :2298
+        return eval({c}, {{PANDRS_HIP_EVAL_COL, 0}, {PANDRS_HIP_EVAL_CONST, st.mean}, {PANDRS_HIP_EVAL_SUB, 0}, {PANDRS_HIP_EVAL_CONST, std_dev},
+                          {PANDRS_HIP_EVAL_DIV, 0}});
+    }
+    // the per-frame lists: every Int64 / Float64 column in column order, PANDRS_HIP_MOMENTS_MAX_COLUMNS per call
+    std::vector<std::pair<std::string, pandrs_hip_moments_stats>> moments_all(uint32_t want) const {
+        std::vector<std::string> names;
+        for (size_t i = 0; i < columns.size(); i++)
+            if (columns[i].index() <= 1) names.push_back(column_names[i]);
+        std::vector<std::pair<std::string, pandrs_hip_moments_stats>> out;
+        for (size_t i = 0; i < names.size(); i += PANDRS_HIP_MOMENTS_MAX_COLUMNS) {
+            const size_t k = std::min(names.size() - i, (size_t)PANDRS_HIP_MOMENTS_MAX_COLUMNS);
+            std::vector<pandrs_hip_column> v;
+            for (size_t j = 0; j < k; j++) v.push_back(view_of(names[i + j]));
+            std::vector<pandrs_hip_moments_stats> st(k);
+            detail::check(pandrs_hip_moments(detail::context(), mem_space(), v.data(), (int32_t)k, (int64_t)row_count_, want, st.data()));
+            for (size_t j = 0; j < k; j++) out.emplace_back(names[i + j], st[j]);
+        }
+        return out;
+    }
+    using NamedValues = std::vector<std::pair<std::string, double>>;
+    NamedValues sum_all() const {                                               // functions.rs:934-943
+        NamedValues r;
+        for (auto &e : moments_all(0)) r.emplace_back(e.first, e.second.sum);
+        return r;
+    }
+    NamedValues mean_all() const {                                              // :944-957
+        NamedValues r;
+        for (auto &e : moments_all(0)) if (e.second.count) r.emplace_back(e.first, e.second.mean);
+        return r;
+    }
+    NamedValues var_all() const {                                               // :975-991
+        NamedValues r;
+        for (auto &e : moments_all(PANDRS_HIP_MOMENTS_WANT_CENTRAL))
+            if (e.second.count > 1) r.emplace_back(e.first, e.second.m2 / (double)(e.second.count - 1));
+        return r;
+    }
+    NamedValues std_all() const {                                               // :958-974
+        NamedValues r = var_all();
+        for (auto &e : r) e.second = std::sqrt(e.second);
+        return r;
+    }
+    NamedValues min_all() const {                                               // :992-1005
+        NamedValues r;
+        for (auto &e : moments_all(0)) if (e.second.count) r.emplace_back(e.first, e.second.min);
+        return r;
+    }
+    NamedValues max_all() const {                                               // :1006-1022
+        NamedValues r;
+        for (auto &e : moments_all(0)) if (e.second.count) r.emplace_back(e.first, e.second.max);
+        return r;
+    }
+    NamedValues product_all() const {                                           // :1583-1595
+        NamedValues r;
+        for (auto &e : moments_all(PANDRS_HIP_MOMENTS_WANT_PROD)) if (e.second.count) r.emplace_back(e.first, e.second.prod);
+        return r;
+    }
+    NamedValues median_all() const {                                            // :1597-1615
+        NamedValues r;
+        for (size_t i = 0; i < columns.size(); i++) {
+            if (columns[i].index() > 1) continue;
+            const auto m = order_stats(column_names[i], {{PANDRS_HIP_OS_MEDIAN, 0.0}});
+            if (m.second) r.emplace_back(column_names[i], m.first[0]);
+        }
+        return r;
+    }
     // value_range / cut / qcut (PandasCompatExt, src/dataframe/pandas_compat/functions.rs:2270-2282, :2339-2420).  value_range:
     // (min, max) over the cells that are not NaN, from the whole-column reduction.  cut: `bins` equal-width bins over that range,
     // the last edge max + 0.001; "(lo, hi]" with two decimals for the first bin with lo <= v < hi, "NaN" for a NaN or null cell,

@@ -18,7 +18,7 @@ STRUCTS = {"pandrs_hip_ctx": "PandrsHipCtx", "pandrs_hip_comm": "PandrsHipComm",
            "pandrs_hip_timings": "PandrsHipTimings", "pandrs_hip_column_stats": "PandrsHipColumnStats",
            "pandrs_hip_window_spec": "PandrsHipWindowSpec", "pandrs_hip_window_quantile_spec": "PandrsHipWindowQuantileSpec",
            "pandrs_hip_describe_stats": "PandrsHipDescribeStats", "pandrs_hip_distinct_info": "PandrsHipDistinctInfo",
-           "pandrs_hip_pivot_info": "PandrsHipPivotInfo"}
+           "pandrs_hip_pivot_info": "PandrsHipPivotInfo", "pandrs_hip_moments_stats": "PandrsHipMomentsStats"}
 OPAQUE = ("pandrs_hip_ctx", "pandrs_hip_comm")
 
 

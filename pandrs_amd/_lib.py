@@ -37,6 +37,10 @@ EVAL_COL, EVAL_CONST, EVAL_ADD, EVAL_SUB, EVAL_MUL, EVAL_DIV, EVAL_REM, EVAL_MAX
 EVAL_MAX_OPS, EVAL_MAX_COLS, EVAL_MAX_DEPTH = 64, 8, 8
 BIN_CUT, BIN_QCUT = range(2)
 BIN_NONE, BIN_NAN, BIN_MAX_BINS = -1, -2, 4096
+MOMENTS_WANT_CENTRAL, MOMENTS_WANT_LOG, MOMENTS_WANT_RECIP, MOMENTS_WANT_PROD = 1, 2, 4, 8
+MOMENTS_MAX_COLUMNS = 16
+OS_AT_FRAC_N, OS_AT_FRAC_N1, OS_MEDIAN, OS_TRIMMED_MEAN = range(4)
+ORDER_STATS_MAX_OPS = 8
 DISTINCT_BY_VALUE, DISTINCT_BY_COUNT = range(2)
 DISTINCT_NUMBER, DISTINCT_NAN, DISTINCT_NULL = range(3)        # the flags of a distinct entry
 PIVOT_ROWS, PIVOT_SUM, PIVOT_MEAN, PIVOT_MIN, PIVOT_MAX, PIVOT_COUNT, PIVOT_LAST = range(7)
@@ -86,6 +90,13 @@ class WindowQuantileSpec(C.Structure):     # pandrs_hip_window_quantile_spec
 class DescribeStats(C.Structure):          # pandrs_hip_describe_stats
     _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("q1", C.c_double),
                 ("median", C.c_double), ("q3", C.c_double), ("max", C.c_double)]
+
+
+class MomentsStats(C.Structure):           # pandrs_hip_moments_stats
+    _fields_ = [("count", C.c_int64), ("count_pos", C.c_int64), ("count_nonzero", C.c_int64), ("sum", C.c_double),
+                ("abs_sum", C.c_double), ("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("m2", C.c_double),
+                ("m3", C.c_double), ("m4", C.c_double), ("abs_dev", C.c_double), ("log_sum", C.c_double),
+                ("recip_sum", C.c_double), ("prod", C.c_double)]
 
 
 class DistinctInfo(C.Structure):           # pandrs_hip_distinct_info
@@ -186,6 +197,9 @@ SYMBOLS = {
     "pandrs_hip_describe": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(DescribeStats)]),
     "pandrs_hip_quantiles": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_double), C.c_int32,
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "pandrs_hip_moments": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int32, C.c_int64, C.c_uint32, C.POINTER(MomentsStats)]),
+    "pandrs_hip_order_stats": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                           C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pandrs_hip_rank": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_int32, _P]),
     "pandrs_hip_fill": (C.c_int32, [_P, C.c_int32, C.POINTER(Column), C.c_int64, C.c_int32, C.c_uint64, C.c_int32, _P, _P,
                                     C.POINTER(C.c_int64)]),

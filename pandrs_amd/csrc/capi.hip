@@ -523,6 +523,20 @@ int32_t pandrs_hip_quantiles(pandrs_hip_ctx *ctx, int32_t mem_space, const pandr
     return pandrs::describe_entry(ctx, mem_space, col, n_rows, percentiles, n_percentiles, out, out_count, nullptr);
 } catch (...) { return pandrs::on_exception("pandrs_hip_quantiles"); }
 
+int32_t pandrs_hip_moments(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows,
+                           uint32_t want, pandrs_hip_moments_stats *out) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "moments: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::moments_entry(ctx, mem_space, cols, n_cols, n_rows, want, out);
+} catch (...) { return pandrs::on_exception("pandrs_hip_moments"); }
+
+int32_t pandrs_hip_order_stats(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
+                               const int32_t *ops, const double *args, int32_t n_ops, double *out, int64_t *out_count) try {
+    if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "order_stats: no context");
+    ST_TRY(pandrs::below_threshold(n_rows));
+    return pandrs::order_stats_entry(ctx, mem_space, col, n_rows, ops, args, n_ops, out, out_count);
+} catch (...) { return pandrs::on_exception("pandrs_hip_order_stats"); }
+
 int32_t pandrs_hip_rank(pandrs_hip_ctx *ctx, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows,
                         int32_t method, int32_t out_mem_space, double *out) try {
     if (!ctx) return fail(PANDRS_HIP_ERR_NOT_INITIALIZED, "rank: no context");

@@ -445,6 +445,12 @@ int32_t describe_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_co
 // order statistics at integer ranks from the radix select), k + 1 doubles, and the number of cells that are neither null nor NaN
 int32_t bin_edges_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, int32_t kind, int32_t k,
                         double *out_edges, int64_t *out_valid);
+// describe.hip: order statistics by the reference's four index rules over the cells that are neither null nor NaN, and the trimmed mean
+int32_t order_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const int32_t *ops,
+                          const double *args, int32_t n_ops, double *out, int64_t *out_count);
+// moments.hip: the fused sums of 1 .. PANDRS_HIP_MOMENTS_MAX_COLUMNS columns in the same launches (want = PANDRS_HIP_MOMENTS_WANT_*)
+int32_t moments_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *cols, int32_t n_cols, int64_t n_rows, uint32_t want,
+                      pandrs_hip_moments_stats *out);
 // bin.hip: per row the i with edges[i] <= v < edges[i + 1] (or PANDRS_HIP_BIN_NONE / PANDRS_HIP_BIN_NAN), and the rows per code
 int32_t bin_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const double *edges, int32_t n_bins,
                   int32_t out_mem_space, int32_t *out_codes, int64_t *out_counts);

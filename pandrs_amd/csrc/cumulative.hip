@@ -41,7 +41,7 @@ struct CumSpans {
 };
 
 // ---- the folds ------------------------------------------------------------------------------------------------------------
-struct ProdState { double m; int64_t e; };              // value = m * 2^e; 0, +-inf and NaN live in m
+// (ProdState and CumProd, the (mantissa, exponent) product: cumulative.hpp, shared with moments.hip)
 
 __device__ __forceinline__ ProdState cum_shfl_up(ProdState v, int d) { return ProdState{__shfl_up(v.m, d, 64), (int64_t)__shfl_up((long long)v.e, d, 64)}; }
 __device__ __forceinline__ ProdState cum_shfl(ProdState v, int l) { return ProdState{__shfl(v.m, l, 64), (int64_t)__shfl((long long)v.e, l, 64)}; }
@@ -49,26 +49,6 @@ __device__ __forceinline__ ProdState cum_shfl(ProdState v, int l) { return ProdS
 __device__ __forceinline__ double cum_mant(double v) { return v; }
 __device__ __forceinline__ double cum_mant(uint32_t) { return 0.0; }
 __device__ __forceinline__ double cum_mant(const ProdState &v) { return v.m; }
-
-struct CumProd {
-    using S = ProdState;
-    static constexpr bool IS_PROD = true, IS_COUNT = false;
-    __device__ static S identity() { return S{1.0, 0}; }
-    __device__ static S start() { return identity(); }  // the reference's fold starts from 1.0
-    __device__ static S norm(double m, int64_t e) {     // 0, +-inf and NaN pass through frexp with exponent 0
-        int ex = 0;
-        const double f = __builtin_frexp(m, &ex);
-        const bool plain = m != 0.0 && m == m && !isinf(m);
-        return S{plain ? f : m, plain ? e + ex : e};
-    }
-    __device__ static S combine(S a, S b) { return norm(a.m * b.m, a.e + b.e); }    // |m| <= 1 on both sides: the product stays in range
-    __device__ static S elem(double x, bool null) { return null ? identity() : norm(x, 0); }
-    __device__ static double value(S s) {
-        const int64_t e = s.e > 4096 ? 4096 : s.e < -4096 ? -4096 : s.e;
-        return __builtin_ldexp(s.m, (int)e);
-    }
-    __device__ static uint64_t out(S s) { return cum_bits(value(s)); }
-};
 
 // ---- one tile's loads -------------------------------------------------------------------------------------------------------
 // the lane's two cells of the load that starts at row r0 (even); rows at or past n read as 0

@@ -66,6 +66,28 @@ struct CumCount {
     __device__ static uint64_t out(S s) { return (uint64_t)s; }
 };
 
+// the state of a product (pandrs_hip_cumulative PROD, pandrs_hip_moments prod): value = m * 2^e; 0, +-inf and NaN live in m
+struct ProdState { double m; int64_t e; };
+struct CumProd {
+    using S = ProdState;
+    static constexpr bool IS_PROD = true, IS_COUNT = false;
+    __device__ static S identity() { return S{1.0, 0}; }
+    __device__ static S start() { return identity(); }  // the reference's fold starts from 1.0
+    __device__ static S norm(double m, int64_t e) {     // 0, +-inf and NaN pass through frexp with exponent 0
+        int ex = 0;
+        const double f = __builtin_frexp(m, &ex);
+        const bool plain = m != 0.0 && m == m && !isinf(m);
+        return S{plain ? f : m, plain ? e + ex : e};
+    }
+    __device__ static S combine(S a, S b) { return norm(a.m * b.m, a.e + b.e); }    // |m| <= 1 on both sides: the product stays in range
+    __device__ static S elem(double x, bool null) { return null ? identity() : norm(x, 0); }
+    __device__ static double value(S s) {
+        const int64_t e = s.e > 4096 ? 4096 : s.e < -4096 ? -4096 : s.e;
+        return __builtin_ldexp(s.m, (int)e);
+    }
+    __device__ static uint64_t out(S s) { return cum_bits(value(s)); }
+};
+
 // ---- host -------------------------------------------------------------------------------------------------------------------------
 static bool cum_overlap(const void *a, size_t na, const void *b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);

@@ -23,7 +23,7 @@
 //    instead of percentiles: QCUT(q) asks for min((uint64)((double)m * (double)i / (double)q), m - 1), i = i0 .. i0 + n, m the
 //    count of those cells, known in step 2.  Up to DS_MAX_SLOTS ranks per selection, every weight zero: ds_finish_ranks_kernel
 //    returns the decoded elements with min, max and m.  CUT needs min and max only: steps 1 and 2, no selection.
-#include "engine.hpp"
+#include "describe.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,28 +32,22 @@
 
 namespace pandrs {
 
-constexpr int DS_THREADS = 256;
-constexpr int DS_LOADS = 4;                              // 16-byte loads in flight per thread
-constexpr int DS_TILE = DS_THREADS * DS_LOADS * 2;       // rows per workgroup iteration (2048; pandrs_hip.h: describe_tile_rows)
-constexpr int DS_BLOCKS_PER_CU = 4;                      // grid = min(4 x CUs, tiles): what the digit stream's 33 KB of LDS keeps
-                                                         // resident per CU, so no launch runs in two rounds (pandrs_hip.h)
+// (DS_THREADS, DS_LOADS, DS_TILE, DS_BLOCKS_PER_CU, the column view and the stream: describe.hpp)
 constexpr int DS_MAX_P = 16;                             // percentiles per call
 constexpr int DS_MAX_SLOTS = 2 * DS_MAX_P;               // distinct target ranks (lo and hi of each)
+constexpr int DS_MAX_OS = 8;                             // order statistics per call, two ranks each at the most
+static_assert(2 * DS_MAX_OS <= DS_MAX_SLOTS, "the ranks of one order-statistics call fit the selection's slots");
 constexpr int DS_DIGIT = 8, DS_BINS = 1 << DS_DIGIT;
 constexpr int DS_MAX_PASSES = 64 / DS_DIGIT;
 constexpr int DS_PEEL = 4;                               // (group, digit) pairs a wave folds by ballot before plain atomics
-
-struct DsCol {
-    const uint64_t *data;     // 8-byte aligned
-    const uint8_t *null;      // LSB-first, 1 = null, any byte offset
-    int64_t n;
-    int i64;
-};
 
 struct DsReq {
     double p[DS_MAX_P];
     int32_t n_p;
     int32_t rank_q, rank_i0, rank_n;      // ranks by number: QCUT(rank_q)'s ranks i0 .. i0 + rank_n (rank_n <= DS_MAX_SLOTS; n_p is 0 then)
+    int32_t n_os;                         // order statistics by the reference's index rules (n_p and rank_n are 0 then)
+    int32_t os_op[DS_MAX_OS];             // pandrs_hip_order_stat, or -1: the host has answered NaN (an argument the reference refuses)
+    double os_arg[DS_MAX_OS];
 };
 
 struct DsPart {               // one workgroup's moments
@@ -72,61 +66,9 @@ struct DsState {
     int32_t s_group[DS_MAX_SLOTS];        // -1: the rank lies in the NaN block
     uint64_t g_prefix[DS_MAX_SLOTS];      // the digits of d chosen so far
     int32_t r_slot[DS_MAX_SLOTS];         // ranks by number: the slot of each requested rank
+    int32_t o_lo[DS_MAX_OS], o_hi[DS_MAX_OS];   // order statistics: the slots of the op's one or two ranks, -1 = none (the result is NaN)
+    uint64_t o_t[DS_MAX_OS];              // TRIMMED_MEAN: t, the cells cut from either end
 };
-
-__device__ __forceinline__ bool ds_is_nan(uint64_t b, int i64) { return !i64 && (b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
-__device__ __forceinline__ double ds_value(uint64_t b, int i64) { return i64 ? (double)(int64_t)b : __longlong_as_double((long long)b); }
-__device__ __forceinline__ uint64_t ds_code(uint64_t b, int i64) { return i64 ? enc_i64((int64_t)b) : enc_f64(__longlong_as_double((long long)b)); }
-__device__ __forceinline__ double ds_decode(uint64_t code, int i64) { return i64 ? (double)dec_i64(code) : dec_f64(code); }
-
-// f(bits, valid) for every row, called by all threads of the workgroup together (f may ballot).  A thread's rows depend on
-// the row numbers only, never on the address, so every floating-point fold has one order and a column gives the same bits
-// wherever it lies.  A data pointer that is 8 bytes off a 16-byte boundary takes its row pairs as two 8-byte loads.
-template <class F>
-__device__ __forceinline__ void ds_stream(const DsCol &c, F &&f) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(c.data) & 15) == 0;
-    const int64_t tiles = (c.n + DS_TILE - 1) / DS_TILE;
-    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const int64_t r0 = t * DS_TILE + 2 * (int64_t)threadIdx.x;
-        uint64_t v[DS_LOADS][2];
-        uint32_t ok[DS_LOADS];
-#pragma unroll
-        for (int k = 0; k < DS_LOADS; k++) {
-            const int64_t r = r0 + (int64_t)k * 2 * DS_THREADS;          // even: both rows' mask bits lie in one byte
-            uint32_t in = 0;
-            v[k][0] = v[k][1] = 0;
-            if (r + 1 < c.n) {
-                if (aligned) {
-                    const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(c.data + r);
-                    v[k][0] = q.x; v[k][1] = q.y;
-                } else {
-                    v[k][0] = c.data[r]; v[k][1] = c.data[r + 1];
-                }
-                in = 3;
-            } else if (r < c.n) {
-                v[k][0] = c.data[r];
-                in = 1;
-            }
-            if (c.null && in) in &= ~((uint32_t)c.null[r >> 3] >> (r & 7));
-            ok[k] = in;
-        }
-#pragma unroll
-        for (int k = 0; k < DS_LOADS; k++) {
-            f(v[k][0], (ok[k] & 1) != 0);
-            f(v[k][1], (ok[k] & 2) != 0);
-        }
-    }
-}
-
-__device__ __forceinline__ double ds_block_sum(double v, double *sh) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = sh[0];
-    for (int w = 1; w < DS_THREADS / 64; w++) r += sh[w];
-    __syncthreads();
-    return r;
-}
 
 // (sum, nn, nan, mn, mx) over the workgroup; the result is valid in thread 0
 __device__ __forceinline__ DsPart ds_block_part(DsPart p, double *shd, uint64_t *shu) {
@@ -217,6 +159,40 @@ __global__ __launch_bounds__(DS_THREADS) void ds_ranks_kernel(const DsPart *part
         const uint64_t idx = (uint64_t)((double)n_num * (double)(req.rank_i0 + j) / (double)req.rank_q);
         tgt[n_t++] = rk[j] = idx < n_num - 1 ? idx : n_num - 1;
     }
+    uint64_t olo[DS_MAX_OS], ohi[DS_MAX_OS];
+    const int n_o = min(req.n_os, DS_MAX_OS);
+    for (int j = 0; j < n_o; j++) {                      // the reference's four index rules over its sorted `valid` (m = n_num cells)
+        const uint64_t m = n_num;
+        const double a = req.os_arg[j];
+        const uint64_t none = ~0ull;
+        olo[j] = ohi[j] = none;
+        st->o_t[j] = 0;
+        if (!m) continue;
+        switch (req.os_op[j]) {
+        case PANDRS_HIP_OS_AT_FRAC_N: {                  // aggregations.rs:87-89, :152-153; `as usize` saturates at 0; get() past the end: NaN
+            const uint64_t r = a > 0.0 ? (uint64_t)fmin((double)m * a, 1.8e19) : 0;
+            if (r < m) olo[j] = ohi[j] = r;
+            break;
+        }
+        case PANDRS_HIP_OS_AT_FRAC_N1: {                 // :198
+            const uint64_t r = a > 0.0 ? (uint64_t)fmin((double)(m - 1) * a, 1.8e19) : 0;
+            if (r < m) olo[j] = ohi[j] = r;
+            break;
+        }
+        case PANDRS_HIP_OS_MEDIAN:                       // functions.rs:1604-1609
+            ohi[j] = m / 2;
+            olo[j] = m % 2 == 0 ? m / 2 - 1 : m / 2;
+            break;
+        case PANDRS_HIP_OS_TRIMMED_MEAN: {               // aggregations.rs:217-218; an empty slice is NaN (:220-222)
+            const uint64_t t = a > 0.0 ? (uint64_t)fmin((double)m * a, 1.8e19) : 0;
+            st->o_t[j] = t;
+            if (t < m - t) { olo[j] = t; ohi[j] = m - 1 - t; }
+            break;
+        }
+        default: break;                                  // -1: answered by the host
+        }
+        if (olo[j] != none) { tgt[n_t++] = olo[j]; tgt[n_t++] = ohi[j]; }
+    }
     for (int a = 1; a < n_t; a++) {                      // ascending, then distinct
         const uint64_t x = tgt[a];
         int b = a - 1;
@@ -240,6 +216,13 @@ __global__ __launch_bounds__(DS_THREADS) void ds_ranks_kernel(const DsPart *part
     for (int j = 0; j < n_r; j++)
         for (int s = 0; s < n_s; s++)
             if (st->s_rank[s] == rk[j]) st->r_slot[j] = s;
+    for (int j = 0; j < n_o; j++) {
+        st->o_lo[j] = st->o_hi[j] = -1;
+        for (int s = 0; s < n_s && olo[j] != ~0ull; s++) {
+            if (st->s_rank[s] == olo[j]) st->o_lo[j] = s;
+            if (st->s_rank[s] == ohi[j]) st->o_hi[j] = s;
+        }
+    }
     const uint64_t span = n_num ? p.mx - p.mn : 0;
     const int width = span ? 64 - __clzll((long long)span) : 0;
     st->n_slots = n_s;
@@ -432,11 +415,12 @@ constexpr size_t DS_HIST_N = (size_t)DS_MAX_SLOTS * DS_BINS;
 constexpr size_t DS_DESCRIBE_OUT = 1 + DS_MAX_P + sizeof(pandrs_hip_describe_stats) / 8;
 constexpr size_t DS_OUT_DOUBLES = DS_DESCRIBE_OUT > (size_t)DS_RANK_OUT ? DS_DESCRIBE_OUT : (size_t)DS_RANK_OUT;
 
-static int32_t ds_work(pandrs_hip_ctx *c, int64_t n, const char *who, DsWork &w) {
+static int32_t ds_work(pandrs_hip_ctx *c, int64_t n, const char *who, DsWork &w, size_t extra_per_workgroup = 0) {
     const int64_t tiles = (n + DS_TILE - 1) / DS_TILE;
     w.grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * DS_BLOCKS_PER_CU, tiles));
     ST_TRY(c->temp.ensure(Arena::padded((size_t)w.grid * sizeof(DsPart)) + Arena::padded((size_t)w.grid * 8) + Arena::padded(DS_HIST_N * 4) +
-                          Arena::padded(sizeof(DsState)) + Arena::padded(DS_OUT_DOUBLES * 8) + 4096, c->stream));
+                          Arena::padded(sizeof(DsState)) + Arena::padded(DS_OUT_DOUBLES * 8) + Arena::padded((size_t)w.grid * extra_per_workgroup) + 4096,
+                          c->stream));
     w.part = c->temp.take<DsPart>((size_t)w.grid);
     w.ssq_part = c->temp.take<double>((size_t)w.grid);
     w.hist = c->temp.take<uint32_t>(DS_HIST_N);
@@ -599,6 +583,150 @@ int32_t bin_edges_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_c
     const double width = (mx - mn) / (double)k;
     for (int32_t i = 0; i <= k; i++) out_edges[i] = mn + (double)i * width;
     out_edges[k] = mx + 0.001;
+    return 0;
+}
+
+// ---- 6. order statistics by the reference's index rules (pandrs_hip_order_stats) ---------------------------------------------------
+// Steps 1 to 3 with the ranks of ds_ranks_kernel's four rules, counted over the cells that are neither null nor NaN.  TRIMMED_MEAN
+// then takes one band stream: the sum of the cells whose code lies strictly between the two selected codes, and how many cells lie
+// below, on the lower code, on the upper code and above; the finish adds the cut values as often as the sorted slice holds them.
+struct DsBand {
+    double sum;
+    uint64_t below, eq_lo, eq_hi, above;
+};
+
+__device__ __forceinline__ uint64_t ds_slot_code(const DsState *st, int slot) { return st->mn + st->g_prefix[st->s_group[slot]]; }
+
+__global__ __launch_bounds__(DS_THREADS) void ds_band_kernel(DsCol c, const DsState *st, int op, DsBand *part) {
+    __shared__ double shd[DS_THREADS / 64];
+    __shared__ uint64_t shu[DS_THREADS / 64];
+    const int sl = st->o_lo[op], sh = st->o_hi[op];
+    if (sl < 0 || sh < 0) return;                        // (uniform) an empty slice or no cell: NaN without a stream
+    const uint64_t lo = ds_slot_code(st, sl), hi = ds_slot_code(st, sh);
+    DsBand b{-0.0, 0, 0, 0, 0};
+    ds_stream(c, [&](uint64_t bits, bool ok) {
+        if (!ok || ds_is_nan(bits, c.i64)) return;
+        const uint64_t e = ds_code(bits, c.i64);
+        if (e < lo) b.below++;
+        else if (e == lo) b.eq_lo++;
+        else if (e < hi) b.sum += ds_value(bits, c.i64);
+        else if (e == hi) b.eq_hi++;
+        else b.above++;
+    });
+    b.sum = ds_block_sum(b.sum, shd);
+    b.below = ds_block_count(b.below, shu);
+    b.eq_lo = ds_block_count(b.eq_lo, shu);
+    b.eq_hi = ds_block_count(b.eq_hi, shu);
+    b.above = ds_block_count(b.above, shu);
+    if (threadIdx.x == 0) part[(size_t)op * gridDim.x + blockIdx.x] = b;
+}
+
+// out: [0] m, the cells that are neither null nor NaN (int64), [1 .. 1 + n_os) the results
+__global__ __launch_bounds__(DS_THREADS) void ds_finish_os_kernel(const DsState *st, DsReq req, int i64, const DsBand *part, int n_part, double *out) {
+    __shared__ double shd[DS_THREADS / 64];
+    __shared__ uint64_t shu[DS_THREADS / 64];
+    const uint64_t m = st->nn - st->nan;
+    if (threadIdx.x == 0) reinterpret_cast<int64_t *>(out)[0] = (int64_t)m;
+    for (int j = 0; j < req.n_os && j < DS_MAX_OS; j++) {
+        const int sl = st->o_lo[j], sh = st->o_hi[j];
+        if (sl < 0 || sh < 0) {                          // (uniform)
+            if (threadIdx.x == 0) out[1 + j] = NAN;
+            continue;
+        }
+        const double v_lo = ds_decode(ds_slot_code(st, sl), i64), v_hi = ds_decode(ds_slot_code(st, sh), i64);
+        if (req.os_op[j] != PANDRS_HIP_OS_TRIMMED_MEAN) {
+            if (threadIdx.x == 0) out[1 + j] = req.os_op[j] == PANDRS_HIP_OS_MEDIAN && sl != sh ? (v_lo + v_hi) / 2.0 : v_lo;
+            continue;
+        }
+        DsBand b{-0.0, 0, 0, 0, 0};
+        for (int i = threadIdx.x; i < n_part; i += DS_THREADS) {
+            const DsBand q = part[(size_t)j * n_part + i];
+            b.sum += q.sum; b.below += q.below; b.eq_lo += q.eq_lo; b.eq_hi += q.eq_hi; b.above += q.above;
+        }
+        b.sum = ds_block_sum(b.sum, shd);
+        b.below = ds_block_count(b.below, shu);
+        b.eq_lo = ds_block_count(b.eq_lo, shu);
+        b.eq_hi = ds_block_count(b.eq_hi, shu);
+        b.above = ds_block_count(b.above, shu);
+        if (threadIdx.x != 0) continue;
+        const uint64_t t = st->o_t[j], kept = m - 2 * t;
+        double num;
+        if (ds_slot_code(st, sl) == ds_slot_code(st, sh)) num = (double)kept * v_lo;       // both cuts select one code: the slice holds nothing else
+        else num = b.sum + (double)(b.below + b.eq_lo - t) * v_lo + (double)(b.eq_hi + b.above - t) * v_hi;
+        out[1 + j] = num / (double)kept;                 // aggregations.rs:224
+    }
+}
+
+int32_t order_stats_entry(pandrs_hip_ctx *c, int32_t mem_space, const pandrs_hip_column *col, int64_t n_rows, const int32_t *ops,
+                          const double *args, int32_t n_ops, double *out, int64_t *out_count) {
+    if (!c || !col || n_rows < 0 || (n_rows > 0 && !col->data) || !ops || !args || !out || !out_count)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: bad arguments");
+    ST_TRY(check_mem_space("order_stats", mem_space));
+    if (col->dtype != PANDRS_HIP_I64 && col->dtype != PANDRS_HIP_F64)
+        return fail(PANDRS_HIP_ERR_TYPE_MISMATCH, "order_stats: the column has dtype %d, expected I64 or F64", col->dtype);
+    if (n_ops < 1 || n_ops > DS_MAX_OS)
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: %d ops; one call takes 1 to %d (two ranks each, %d slots)", n_ops, DS_MAX_OS,
+                    DS_MAX_SLOTS);
+    DsReq req{};
+    req.n_os = n_ops;
+    bool band = false;
+    for (int j = 0; j < n_ops; j++) {
+        const double a = args[j];
+        if (ops[j] < PANDRS_HIP_OS_AT_FRAC_N || ops[j] > PANDRS_HIP_OS_TRIMMED_MEAN)
+            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: op %d is %d, not a pandrs_hip_order_stat", j, ops[j]);
+        if (a != a && ops[j] != PANDRS_HIP_OS_MEDIAN)
+            return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: the argument of op %d is NaN", j);
+        req.os_op[j] = ops[j];
+        req.os_arg[j] = a;
+        // the reference's early returns, decided before any launch: percentile_value's q (aggregations.rs:185), trimmed_mean's fraction (:204)
+        if ((ops[j] == PANDRS_HIP_OS_AT_FRAC_N1 && (a < 0.0 || a > 1.0)) || (ops[j] == PANDRS_HIP_OS_TRIMMED_MEAN && (a < 0.0 || a >= 0.5)))
+            req.os_op[j] = -1;
+        band = band || req.os_op[j] == PANDRS_HIP_OS_TRIMMED_MEAN;
+    }
+    if (n_rows >= (int64_t(1) << 32))
+        return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: %lld rows; one call takes fewer than 2^32", (long long)n_rows);
+    *out_count = 0;
+    for (int j = 0; j < n_ops; j++) out[j] = NAN;
+    if (n_rows == 0) return 0;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    timings_begin(c);
+    const int64_t n = n_rows;
+    DsWork w{};
+    ST_TRY(ds_work(c, n, "order_stats", w, (size_t)DS_MAX_OS * sizeof(DsBand)));
+    DsBand *band_part = c->temp.take<DsBand>((size_t)w.grid * DS_MAX_OS);
+    if (!band_part) return fail(PANDRS_HIP_ERR_OUT_OF_MEMORY, "workspace too small (order_stats)");
+    ColView cv{col->data, col->null_mask};
+    Stager stg{c, mem_space};
+    if (const size_t need = stg.col_size(*col, n)) {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_STAGE_IN);
+        ST_TRY(stg.reserve(need));
+        cv = stg.col(*col, n);
+        if (stg.status) return stg.status;
+    }
+    if (reinterpret_cast<uintptr_t>(cv.data) & 7) return fail(PANDRS_HIP_ERR_INVALID_ARGUMENT, "order_stats: the column must be 8-byte aligned");
+    const DsCol dc{static_cast<const uint64_t *>(cv.data), cv.mask, n, col->dtype == PANDRS_HIP_I64 ? 1 : 0};
+    double *h_out = static_cast<double *>(c->pinned);
+    int n_band = 0;
+    {
+        PhaseTimer pt(c, PANDRS_HIP_PHASE_OTHER);
+        ST_TRY(ds_enqueue(c, dc, req, w, true));
+        for (int j = 0; j < n_ops; j++)
+            if (req.os_op[j] == PANDRS_HIP_OS_TRIMMED_MEAN) {
+                hipLaunchKernelGGL(ds_band_kernel, dim3(w.grid), dim3(DS_THREADS), 0, c->stream, dc, (const DsState *)w.st, j, band_part);
+                n_band++;
+            }
+        hipLaunchKernelGGL(ds_finish_os_kernel, dim3(1), dim3(DS_THREADS), 0, c->stream, (const DsState *)w.st, req, dc.i64, (const DsBand *)band_part,
+                           w.grid, w.d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h_out, w.d_out, (size_t)(1 + DS_MAX_OS) * 8, hipMemcpyDeviceToHost, c->stream));
+    c->timings.n_partitions = n_band;                    // the band streams behind the selection
+    c->timings.algorithmic_bytes = (int64_t)n * 8 + (col->null_mask ? (n + 7) / 8 : 0);          // the column (+ mask), once
+    ST_TRY(timings_end(c));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out_count = reinterpret_cast<const int64_t *>(h_out)[0];
+    for (int j = 0; j < n_ops; j++) out[j] = h_out[1 + j];
     return 0;
 }
 

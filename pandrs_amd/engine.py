@@ -779,6 +779,38 @@ class Context:
                                              out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
         return out[:ps.shape[0]], cnt.value
 
+    # -- shape statistics (fused sums of many columns; order statistics by the reference's index rules) -----------------
+    def moments(self, cols, n_rows, want=0):
+        """The fused sums of 1 to L.MOMENTS_MAX_COLUMNS I64 / F64 columns of n_rows rows each, in the same launches
+        (pandrs_hip_moments; the sums behind PandasCompatExt::skew / kurtosis / sem / mad / prod / cv / geometric_mean /
+        harmonic_mean / var_column / range / abs_sum / zscore and the *_all lists).  `cols`: (data, mask, dtype) triples, all
+        on the host or all on the device, or ResidentColumns.  `want`: L.MOMENTS_WANT_CENTRAL | _LOG | _RECIP | _PROD; a
+        field whose bit is clear is NaN.  Cells that are null or NaN do not count.  -> a list of dicts, one per column, with
+        the fields of pandrs_hip_moments_stats."""
+        cols = [tuple(c) for c in cols]
+        keep = []
+        cc, sp = self._cols(cols, keep)
+        out = (L.MomentsStats * max(len(cols), 1))()
+        _check(self.lib.pandrs_hip_moments(self.h, sp, cc, len(cols), int(n_rows), int(want), out))
+        return [{name: getattr(out[i], name) for name, _ in L.MomentsStats._fields_} for i in range(len(cols))]
+
+    def order_stats(self, col, n_rows, ops):
+        """Order statistics of one I64 / F64 column by the reference's index rules, and the trimmed mean, on the device
+        (pandrs_hip_order_stats; PandasCompatExt::iqr / describe_column / percentile_value / trimmed_mean / median_all).
+        `col` as in describe; `ops`: 1 to L.ORDER_STATS_MAX_OPS pairs (op, arg) with op L.OS_AT_FRAC_N / _AT_FRAC_N1 /
+        _MEDIAN / _TRIMMED_MEAN.  -> (float64 numpy array, one value per pair; m, the cells that are neither null nor NaN)."""
+        cc, sp, keep = self._col(col)
+        ops = list(ops)
+        k = len(ops)
+        op = np.ascontiguousarray([int(o) for o, _ in ops], dtype=np.int32).reshape(-1)
+        arg = np.ascontiguousarray([float(a) for _, a in ops], dtype=np.float64).reshape(-1)
+        out = np.empty(max(k, 1), np.float64)
+        cnt = C.c_int64(0)
+        _check(self.lib.pandrs_hip_order_stats(self.h, sp, cc, int(n_rows), op.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               arg.ctypes.data_as(C.POINTER(C.c_double)), k,
+                                               out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
+        return out[:k], cnt.value
+
     # -- rank (radix sort, tie-run boundaries, scatter) ------------------------------------------------------------
     def rank(self, col, n_rows, method, out=None, out_device=None):
         """The ascending 1-based rank of every row of one I64 / F64 column on the device (pandrs_hip_rank;

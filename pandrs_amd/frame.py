@@ -330,6 +330,29 @@ def _key_strings(dtype, cells, nulls, null_string="NULL"):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- f64 arithmetic as Rust does it
+_F64_EPSILON = 2.0 ** -52          # f64::EPSILON
+
+
+def _fdiv(a, b):
+    """a / b by IEEE rules (Python raises on a zero divisor)."""
+    if b == 0.0:
+        if a == 0.0 or math.isnan(a):
+            return math.nan
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+    return a / b
+
+
+def _fsqrt(x):
+    """f64::sqrt: NaN for a negative or NaN operand (math.sqrt raises on the former)."""
+    return math.nan if math.isnan(x) or x < 0.0 else math.sqrt(x)
+
+
+def _fexp(x):
+    """f64::exp: +inf past the range (math.exp raises)."""
+    return math.inf if x > 709.782712893384 else math.exp(x)
+
+
 # ---------------------------------------------------------------------------------------------- context
 _default_ctx = None
 
@@ -785,6 +808,232 @@ class OptimizedDataFrame:
         """PandasCompatExt::idxmin (functions.rs:184-192): the row of the smallest value, the FIRST one among equals
         (Iterator::min_by), NaN and null cells skipped; None when the column holds no number.  One device pass."""
         return self._idx_extreme(column, 0)
+
+    # -- shape statistics (dataframe/pandas_compat/functions.rs:1617-1665, helpers/aggregations.rs:8-225) ----------------
+    # Every method: one pandrs_hip_moments call (two streams at the most over the column, whatever it asks for) and/or one
+    # pandrs_hip_order_stats call, then the reference's expression on the host over the returned fields.  The cells that count
+    # are neither null nor NaN.  Errors before any device call: ColumnNotFound, ColumnTypeMismatch for a String or Boolean column.
+    def _moments(self, column, want):
+        c = self._numeric(column)
+        return get_context().moments([c.view()], c.len(), want)[0]
+
+    def _order_stats(self, column, ops):
+        c = self._numeric(column)
+        return get_context().order_stats(c.view(), c.len(), ops)
+
+    def skew(self, column):
+        """skew (functions.rs:1617-1640): NaN below 3 valid cells (:1621) and for std_dev == 0.0 (:1630); m3 / std_dev.powi(3)
+        with the population variance (:1627), times sqrt(n (n - 1)) / (n - 2) (:1638)."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] < 3:
+            return math.nan
+        n = float(st["count"])
+        std_dev = _fsqrt(st["m2"] / n)
+        if std_dev == 0.0:
+            return math.nan
+        skewness = _fdiv(st["m3"] / n, (std_dev * std_dev) * std_dev)
+        return skewness * (_fsqrt(n * (n - 1.0)) / (n - 2.0))
+
+    def kurtosis(self, column):
+        """kurtosis (functions.rs:1642-1665): NaN below 4 valid cells (:1646) and for std_dev == 0.0 (:1655); m4 /
+        std_dev.powi(4) - 3.0 (:1660), adjusted as (n - 1) / ((n - 2) (n - 3)) * ((n + 1) k + 6) (:1663)."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] < 4:
+            return math.nan
+        n = float(st["count"])
+        std_dev = _fsqrt(st["m2"] / n)
+        if std_dev == 0.0:
+            return math.nan
+        kurt = _fdiv(st["m4"] / n, (std_dev * std_dev) * (std_dev * std_dev)) - 3.0
+        return ((n - 1.0) / ((n - 2.0) * (n - 3.0))) * ((n + 1.0) * kurt + 6.0)
+
+    def var_column(self, column, ddof=1):
+        """var_column (functions.rs:3571-3584): NaN for count <= ddof (:3575), else sum (v - mean)^2 / (n - ddof) (:3581)."""
+        ddof = int(ddof)
+        if ddof < 0:
+            raise InvalidValue("ddof must not be negative, got %d" % ddof)
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] <= ddof:
+            return math.nan
+        return st["m2"] / (float(st["count"]) - float(ddof))
+
+    def std_column(self, column, ddof=1):
+        """std_column (functions.rs:3586-3588): var_column(column, ddof).sqrt()."""
+        return _fsqrt(self.var_column(column, ddof))
+
+    def sem(self, column, ddof=1):
+        """sem (aggregations.rs:8-23): NaN for count <= ddof (:12); sqrt(sum (v - mean)^2 / (count - ddof)) / sqrt(n) (:18-22)."""
+        ddof = int(ddof)
+        if ddof < 0:
+            raise InvalidValue("ddof must not be negative, got %d" % ddof)
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] <= ddof:
+            return math.nan
+        variance = st["m2"] / float(st["count"] - ddof)
+        return _fsqrt(variance) / math.sqrt(float(st["count"]))
+
+    def mad(self, column):
+        """mad (aggregations.rs:26-39): the mean absolute deviation sum |v - mean| / count (:35-36); NaN without a valid cell (:30)."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] == 0:
+            return math.nan
+        return st["abs_dev"] / float(st["count"])
+
+    def prod(self, column):
+        """prod (aggregations.rs:42-51): the product of the valid cells; NaN without one (:46).  A range excursion of finite
+        cells is not sticky here (pandrs_hip.h, pandrs_hip_moments)."""
+        st = self._moments(column, L.MOMENTS_WANT_PROD)
+        return st["prod"] if st["count"] else math.nan
+
+    def range(self, column):
+        """range (functions.rs:4207-4219): max - min over the valid cells; NaN without one (:4211)."""
+        st = self._moments(column, 0)
+        return st["max"] - st["min"] if st["count"] else math.nan
+
+    def abs_sum(self, column):
+        """abs_sum (functions.rs:4221-4224): sum |v| over the valid cells."""
+        return self._moments(column, 0)["abs_sum"]
+
+    def cv(self, column):
+        """cv (aggregations.rs:162-181): NaN without a valid cell (:166) and for mean.abs() < EPSILON (:173); sqrt(sum (v -
+        mean)^2 / (n - 1.0).max(1.0)) / mean.abs() (:177-180)."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] == 0:
+            return math.nan
+        n, mean = float(st["count"]), st["mean"]
+        if abs(mean) < _F64_EPSILON:
+            return math.nan
+        return _fdiv(_fsqrt(st["m2"] / max(n - 1.0, 1.0)), abs(mean))
+
+    def geometric_mean(self, column):
+        """geometric_mean (aggregations.rs:108-122): exp(sum ln v / count) over the cells > 0 (:110-114); NaN without one."""
+        st = self._moments(column, L.MOMENTS_WANT_LOG)
+        if st["count_pos"] == 0:
+            return math.nan
+        return _fexp(st["log_sum"] / float(st["count_pos"]))
+
+    def harmonic_mean(self, column):
+        """harmonic_mean (aggregations.rs:125-139): count / sum (1.0 / v) over the cells != 0.0 (:127-131); NaN without one."""
+        st = self._moments(column, L.MOMENTS_WANT_RECIP)
+        if st["count_nonzero"] == 0:
+            return math.nan
+        return _fdiv(float(st["count_nonzero"]), st["recip_sum"])
+
+    def iqr(self, column):
+        """iqr (aggregations.rs:142-159): sorted[(n * 0.75) as usize] - sorted[(n * 0.25) as usize]; NaN below 2 valid cells (:146)."""
+        (q25, q75), m = self._order_stats(column, [(L.OS_AT_FRAC_N, 0.25), (L.OS_AT_FRAC_N, 0.75)])
+        return math.nan if m < 2 else float(q75) - float(q25)
+
+    def percentile_value(self, column, q):
+        """percentile_value (aggregations.rs:184-200): sorted[((n - 1) * q) as usize]; NaN for q outside [0, 1] (:185), decided
+        before any device call, and without a valid cell (:192).  Deviations: the column is looked up first, so a missing or
+        non-numeric column raises ColumnNotFound / ColumnTypeMismatch even for a q outside [0, 1] (the reference returns NaN
+        there before it looks at the column); a NaN q raises InvalidValue (the reference's comparisons let it through and
+        `NaN as usize` indexes element 0)."""
+        self._numeric(column)
+        q = float(q)
+        if math.isnan(q):
+            raise InvalidValue("q must not be NaN")
+        if q < 0.0 or q > 1.0:
+            return math.nan
+        (v,), _ = self._order_stats(column, [(L.OS_AT_FRAC_N1, q)])
+        return float(v)
+
+    def trimmed_mean(self, column, trim_fraction):
+        """trimmed_mean (aggregations.rs:203-225): the mean of sorted[t .. n - t), t = (n * trim_fraction) as usize; NaN for a
+        fraction outside [0, 0.5) (:204), decided before any device call, without a valid cell (:211) and for an empty slice
+        (:220).  Deviations: the column is looked up first, so a missing or non-numeric column raises ColumnNotFound /
+        ColumnTypeMismatch even for a fraction outside [0, 0.5) (the reference returns NaN there before it looks at the
+        column); a NaN fraction raises InvalidValue (the reference's comparisons let it through and `NaN as usize` trims
+        nothing)."""
+        self._numeric(column)
+        a = float(trim_fraction)
+        if math.isnan(a):
+            raise InvalidValue("trim_fraction must not be NaN")
+        if a < 0.0 or a >= 0.5:
+            return math.nan
+        (v,), _ = self._order_stats(column, [(L.OS_TRIMMED_MEAN, a)])
+        return float(v)
+
+    def describe_column(self, column):
+        """describe_column (aggregations.rs:54-105): {count, mean, std (n - 1, at least 1), min, max, 25%, 50%, 75%} with the
+        quartiles sorted[(n * 0.25) as usize], sorted[n / 2], sorted[(n * 0.75) as usize] (:87-89); without a valid cell only
+        count 0.0 and NaN mean / std / min / max (:60-67).  One moments call plus one order-statistics call."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] == 0:
+            return {"count": 0.0, "mean": math.nan, "std": math.nan, "min": math.nan, "max": math.nan}
+        n = float(st["count"])
+        (q25, q50, q75), _ = self._order_stats(column, [(L.OS_AT_FRAC_N, 0.25), (L.OS_AT_FRAC_N, 0.5), (L.OS_AT_FRAC_N, 0.75)])
+        # (n * 0.5) as usize == n / 2 for every n below 2^53: halving is exact
+        return {"count": n, "mean": st["mean"], "std": _fsqrt(st["m2"] / max(n - 1.0, 1.0)), "min": st["min"], "max": st["max"],
+                "25%": float(q25), "50%": float(q50), "75%": float(q75)}
+
+    def zscore(self, column):
+        """zscore (functions.rs:2284-2314): (v - mean) / std_dev with the sample deviation (n - 1, :2296), NaN stays NaN, -> list
+        of float.  InvalidValue where the reference returns Err: fewer than 2 valid cells (:2288), a deviation of zero (:2298).
+        One moments call plus one pandrs_hip_eval call."""
+        st = self._moments(column, L.MOMENTS_WANT_CENTRAL)
+        if st["count"] < 2:
+            raise InvalidValue("Need at least 2 values for z-score")
+        std_dev = _fsqrt(st["m2"] / (float(st["count"]) - 1.0))
+        if std_dev == 0.0:
+            raise InvalidValue("Standard deviation is zero")
+        out = self._eval_values((col(column) - st["mean"]) / std_dev)
+        values = np.array(out.data, dtype=np.float64)
+        if out.null_mask is not None:                      # a null cell is the mirrors' missing value: NaN, as a NaN cell
+            values[np.unpackbits(np.asarray(out.null_mask, np.uint8), bitorder="little")[:values.shape[0]].astype(bool)] = np.nan
+        return values.tolist()
+
+    def _moments_all(self, want):
+        """[(name, stats)] of every Int64 / Float64 column in column order (the reference's `if let Ok(values) =
+        get_column_numeric_values`): all of them in one call per L.MOMENTS_MAX_COLUMNS columns."""
+        names = [n for n in self.column_names if self.column(n).dtype in (L.I64, L.F64)]
+        out = []
+        for i in range(0, len(names), L.MOMENTS_MAX_COLUMNS):
+            chunk = names[i:i + L.MOMENTS_MAX_COLUMNS]
+            stats = get_context().moments([self.column(n).view() for n in chunk], self._row_count, want)
+            out.extend(zip(chunk, stats))
+        return out
+
+    def sum_all(self):
+        """sum_all (functions.rs:934-943): [(name, sum of the valid cells)] of every numeric column."""
+        return [(n, st["sum"]) for n, st in self._moments_all(0)]
+
+    def mean_all(self):
+        """mean_all (functions.rs:944-957): sum / count; a column without a valid cell is left out (:950)."""
+        return [(n, st["mean"]) for n, st in self._moments_all(0) if st["count"]]
+
+    def var_all(self):
+        """var_all (functions.rs:975-991): sum (v - mean)^2 / (count - 1); a column with fewer than 2 valid cells is left out (:981)."""
+        return [(n, st["m2"] / float(st["count"] - 1)) for n, st in self._moments_all(L.MOMENTS_WANT_CENTRAL) if st["count"] > 1]
+
+    def std_all(self):
+        """std_all (functions.rs:958-974): var_all's values, square-rooted (:969)."""
+        return [(n, _fsqrt(v)) for n, v in self.var_all()]
+
+    def min_all(self):
+        """min_all (functions.rs:992-1005): the fold of f64::min from +inf; a column without a valid cell is left out (:998)."""
+        return [(n, st["min"]) for n, st in self._moments_all(0) if st["count"]]
+
+    def max_all(self):
+        """max_all (functions.rs:1006-1022): the fold of f64::max from -inf; a column without a valid cell is left out (:1012)."""
+        return [(n, st["max"]) for n, st in self._moments_all(0) if st["count"]]
+
+    def product_all(self):
+        """product_all (functions.rs:1583-1595): the product from 1.0; a column without a valid cell is left out (:1588)."""
+        return [(n, st["prod"]) for n, st in self._moments_all(L.MOMENTS_WANT_PROD) if st["count"]]
+
+    def median_all(self):
+        """median_all (functions.rs:1597-1615): (sorted[n/2 - 1] + sorted[n/2]) / 2.0 for even n, else sorted[n/2] (:1604-1609);
+        a column without a valid cell is left out (:1602).  One order-statistics call per numeric column."""
+        out = []
+        for n in self.column_names:
+            c = self.column(n)
+            if c.dtype in (L.I64, L.F64):
+                (v,), m = get_context().order_stats(c.view(), c.len(), [(L.OS_MEDIAN, 0.0)])
+                if m:
+                    out.append((n, float(v)))
+        return out
 
     # -- value_range / cut / qcut (dataframe/pandas_compat/functions.rs:2270-2282, :2339-2420) ----------------------
     def value_range(self, column):
